@@ -36,6 +36,16 @@ from volcano_amd.utils import synth
 
 GI = 1024 ** 3
 
+# --dump-outputs budget: every array of a run together stays under this
+DUMP_BYTES_MAX = 64 * 1000 * 1000
+
+
+def stamp_creation(pg, seq: int) -> None:
+    """Fixed creation time per job sequence number: job order ties break
+    on it, so the inventory is identical from run to run instead of
+    carrying the wall clock of the moment it was built."""
+    pg.meta.creation_timestamp = 1.0e9 + seq * 1.0e-3
+
 
 def build_cluster(cache: SchedulerCache, n_nodes: int, n_jobs: int,
                   pods_per_job: int, rank: int, world: int,
@@ -77,6 +87,7 @@ def build_cluster(cache: SchedulerCache, n_nodes: int, n_jobs: int,
         pg = synth.make_podgroup(name, queue=queue, min_member=size,
                                  min_resources={CPU: cpu * size,
                                                 MEMORY: mem * size})
+        stamp_creation(pg, j)
         job = JobInfo(f"default/{name}", pg)
         for p in range(size):
             pod = synth.make_pod(f"{name}-w-{p}", name, queue=queue,
@@ -102,6 +113,41 @@ def reset_cluster(cache: SchedulerCache, jobs):
     cache.reset_usage()
     if isinstance(cache.binder, FakeBinder):
         cache.binder.clear()
+
+
+def dump_outputs(cache: SchedulerCache, out_dir: str, rank: int) -> None:
+    """Write what the last timed step decided as ``<name>.npy`` (float64).
+
+    ``pod_node``: one entry per pod, jobs and their pods in key order —
+    the index (in node-name order) of the node the pod was bound to, -1
+    for a pod left unbound.  ``node_pod_count``: pods bound per node, same
+    node order.  Ranks other than 0 add ``_rank<r>`` to the name.  Past
+    the byte budget a fixed seeded sample of the entries is kept."""
+    import numpy as np
+    node_idx = {name: i for i, name in enumerate(sorted(cache.nodes))}
+    pod_node = []
+    for jkey in sorted(cache.jobs):
+        tasks = cache.jobs[jkey].tasks
+        for tkey in sorted(tasks):
+            t = tasks[tkey]
+            bound = t.status == TaskStatus.BOUND and t.node_name
+            pod_node.append(node_idx.get(t.node_name, -1) if bound else -1)
+    pod_node = np.asarray(pod_node, dtype=np.float64)
+    placed = pod_node[pod_node >= 0].astype(np.int64)
+    arrays = {
+        "pod_node": pod_node,
+        "node_pod_count": np.bincount(
+            placed, minlength=len(node_idx)).astype(np.float64),
+    }
+    budget = DUMP_BYTES_MAX // len(arrays) // 8      # entries per array
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    for name, arr in arrays.items():
+        if arr.size > budget:
+            keep = np.random.default_rng(20240607).choice(
+                arr.size, size=budget, replace=False)
+            arr = arr[np.sort(keep)]
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), arr)
 
 
 def main():
@@ -136,9 +182,18 @@ def main():
                          "pod_scheduling_latency_seconds)")
     ap.add_argument("--churn-gangs", type=int, default=200,
                     help="new gangs per churn cycle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's "
+                         "placement decisions to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: today the "
+                         "per-phase timing summary of --timing (other "
+                         "shapes and modes have flags of their own)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
-    rank = int(os.environ.get("RANK", "0"))
+    rank =int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     dist = world > 1
     use_gpu = torch.cuda.is_available() and not args.cpu
@@ -221,6 +276,7 @@ def main():
             j = churn_state["i"]
             name = f"churn-{rank}-{j:06d}"
             pg = synth.make_podgroup(name, min_member=args.pods_per_job)
+            stamp_creation(pg, j)
             job = JobInfo(f"default/{name}", pg)
             for p in range(args.pods_per_job):
                 pod = synth.make_pod(f"{name}-w-{p}", name, cpu_milli=1000.0,
@@ -356,7 +412,10 @@ def main():
     else:
         p99 = 0.0
 
-    if args.timing and rank == 0:
+    if args.dump_outputs:
+        dump_outputs(cache, args.dump_outputs, rank)
+
+    if (args.timing or args.full) and rank == 0:
         import sys
         from volcano_amd.utils.metrics import METRICS
         for name in ("open_session_duration",
