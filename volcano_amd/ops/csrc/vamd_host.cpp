@@ -1,0 +1,576 @@
+// _vamd_host: CPython shell around settle_core.h.  One call per cycle
+// replaces the interpreted slot walk of AllocateAction._apply: it settles
+// every class's placement log and performs the per-task object updates
+// (node_name / status stores, node batch appends, per-job bind lists)
+// through direct C-API calls.  Device-side reverts, event handlers, the
+// binder and pod-group updates stay in Python and get their arguments
+// back from here in walk order.
+//
+// Host-only C++ (no HIP); not linked against libpython.
+#define PY_SSIZE_T_CLEAN
+#include <Python.h>
+#include <structmember.h>
+
+#include <cstdint>
+#include <vector>
+
+#include "settle_core.h"
+
+namespace {
+
+struct Ref {                       // owning reference, released on scope exit
+    PyObject* p;
+    explicit Ref(PyObject* o = nullptr) : p(o) {}
+    ~Ref() { Py_XDECREF(p); }
+    Ref(const Ref&) = delete;
+    Ref& operator=(const Ref&) = delete;
+    explicit operator bool() const { return p != nullptr; }
+    PyObject* release() { PyObject* o = p; p = nullptr; return o; }
+    void reset(PyObject* o) { Py_XDECREF(p); p = o; }
+};
+
+struct Buf {                       // contiguous read-only buffer view
+    Py_buffer v;
+    bool held = false;
+    ~Buf() { if (held) PyBuffer_Release(&v); }
+    bool get(PyObject* o, Py_ssize_t itemsize, const char* what) {
+        if (PyObject_GetBuffer(o, &v, PyBUF_C_CONTIGUOUS) != 0) return false;
+        held = true;
+        if (v.itemsize != itemsize) {
+            PyErr_Format(PyExc_TypeError, "%s: expected itemsize %zd, got %zd",
+                         what, itemsize, v.itemsize);
+            return false;
+        }
+        return true;
+    }
+    Py_ssize_t count() const { return v.len / v.itemsize; }
+};
+
+PyObject *s_bundle, *s_log_off, *s_job_key, *s_tclass, *s_tasks, *s_ntasks,
+    *s_min_needed, *s_job, *s_key, *s_name, *s_batches, *s_node_name,
+    *s_status, *s_f, *s_r, *s_task_status_index, *s_occ, *s_alloc_vec;
+
+// Offset of a plain object-valued __slots__ member of `tp`, or -1 when
+// `name` is anything else (property, instance-dict attribute, read-only
+// or typed member) or the type customizes attribute stores.
+Py_ssize_t slot_offset(PyTypeObject* tp, PyObject* name) {
+    if (tp->tp_setattro != PyObject_GenericSetAttr) return -1;
+    Ref d(PyObject_GetAttr(reinterpret_cast<PyObject*>(tp), name));
+    if (!d) {
+        PyErr_Clear();
+        return -1;
+    }
+    if (Py_TYPE(d.p) != &PyMemberDescr_Type) return -1;
+    PyMemberDescrObject* md = reinterpret_cast<PyMemberDescrObject*>(d.p);
+    if (md->d_member->type != T_OBJECT_EX || md->d_member->flags != 0 ||
+        !PyType_IsSubtype(tp, PyDescr_TYPE(md)))
+        return -1;
+    return md->d_member->offset;
+}
+
+// Stores of node_name/status on tasks.  The task type seen first gets its
+// two slot offsets resolved once; its instances are then written in place
+// (what the member descriptor's setter does, minus the lookup).  Every
+// other object goes through PyObject_SetAttr.
+struct TaskStore {
+    Ref type;
+    Py_ssize_t off_node = -1, off_status = -1;
+
+    static void put(PyObject* t, Py_ssize_t off, PyObject* v) {
+        PyObject** slot = reinterpret_cast<PyObject**>(
+            reinterpret_cast<char*>(t) + off);
+        PyObject* old = *slot;
+        Py_INCREF(v);
+        *slot = v;
+        Py_XDECREF(old);
+    }
+
+    bool store(PyObject* t, PyObject* name, PyObject* status) {
+        if (!type) {
+            PyTypeObject* tp = Py_TYPE(t);
+            Py_INCREF(tp);
+            type.reset(reinterpret_cast<PyObject*>(tp));
+            off_node = slot_offset(tp, s_node_name);
+            off_status = slot_offset(tp, s_status);
+        }
+        if (reinterpret_cast<PyObject*>(Py_TYPE(t)) == type.p &&
+            off_node >= 0 && off_status >= 0) {
+            put(t, off_node, name);
+            put(t, off_status, status);
+            return true;
+        }
+        return PyObject_SetAttr(t, s_node_name, name) == 0 &&
+               PyObject_SetAttr(t, s_status, status) == 0;
+    }
+};
+
+// The walk allocates one small list per piece and per job.  With the
+// cyclic collector live, every few hundred of them start a young-
+// generation pass that traverses the lists built so far, task by task —
+// a third of the walk's time at 100k tasks.  None of these lists is
+// garbage before the call returns, so the collector is paused for the
+// bounded duration of the call and catches up on the next allocation.
+struct GcPause {
+#if PY_VERSION_HEX >= 0x030A0000
+    int was = PyGC_Disable();
+    ~GcPause() { if (was) PyGC_Enable(); }
+#endif
+};
+
+struct Walk {
+    TaskStore tstore;
+    PyObject* jobs;
+    PyObject* alias;
+    PyObject* nodes;               // list, node_id order
+    PyObject* bound;
+    bool want_fire;
+    Ref bind_by_job, committed, full, events;
+    std::vector<int64_t> acc_rows, acc_cls;
+    std::vector<double> acc_cnts;
+    long n_committed = 0, n_missed = 0, n_lost = 0, n_tail = 0;
+
+    // Assign pieces [p0, p1) of `so` to the next tasks of `job`.
+    bool commit(PyObject* job, PyObject* tasks, Py_ssize_t c,
+                const vamd::SettleOut& so, size_t p0, size_t p1,
+                bool exact) {
+        Ref key(PyObject_GetAttr(job, s_key));
+        if (!key) return false;
+        PyObject* jl = PyDict_GetItemWithError(bind_by_job.p, key.p);
+        if (jl == nullptr) {
+            if (PyErr_Occurred()) return false;
+            Ref fresh(PyList_New(0));
+            if (!fresh || PyDict_SetItem(bind_by_job.p, key.p, fresh.p) != 0)
+                return false;
+            jl = fresh.p;          // the dict keeps it alive
+        }
+        Ref f_nodes, f_cnts, f_tasks;
+        if (want_fire) {
+            f_nodes.reset(PyList_New(0));
+            f_cnts.reset(PyList_New(0));
+            f_tasks.reset(PyList_New(0));
+            if (!f_nodes || !f_cnts || !f_tasks) return false;
+        }
+        const Py_ssize_t n_nodes = PyList_GET_SIZE(nodes);
+        for (size_t p = p0; p < p1; ++p) {
+            const int32_t nid = so.p_node[p];
+            const int32_t take = so.p_take[p];
+            const int32_t toff = so.p_toff[p];
+            if (nid < 0 || nid >= n_nodes) {
+                PyErr_Format(PyExc_IndexError,
+                             "placement log names node %d of %zd",
+                             static_cast<int>(nid), n_nodes);
+                return false;
+            }
+            PyObject* ni = PyList_GET_ITEM(nodes, nid);
+            Ref name(PyObject_GetAttr(ni, s_name));
+            if (!name) return false;
+            Ref sl(PyList_GetSlice(tasks, toff,
+                                   static_cast<Py_ssize_t>(toff) + take));
+            if (!sl) return false;
+            const Py_ssize_t k = PyList_GET_SIZE(sl.p);
+            if (exact && k != take) {
+                PyErr_SetString(PyExc_RuntimeError,
+                                "class has fewer tasks than its log places");
+                return false;
+            }
+            for (Py_ssize_t i = 0; i < k; ++i) {
+                PyObject* t = PyList_GET_ITEM(sl.p, i);
+                if (!tstore.store(t, name.p, bound)) return false;
+            }
+            Ref batches(PyObject_GetAttr(ni, s_batches));
+            if (!batches) return false;
+            if (!PyList_Check(batches.p)) {
+                PyErr_SetString(PyExc_TypeError, "_batches must be a list");
+                return false;
+            }
+            if (PyList_Append(batches.p, sl.p) != 0) return false;
+            acc_rows.push_back(nid);
+            acc_cnts.push_back(static_cast<double>(take));
+            acc_cls.push_back(c);
+            const Py_ssize_t at = PyList_GET_SIZE(jl);
+            if (PyList_SetSlice(jl, at, at, sl.p) != 0) return false;
+            if (want_fire) {
+                Ref a(PyLong_FromLong(nid)), b(PyLong_FromLong(take));
+                if (!a || !b || PyList_Append(f_nodes.p, a.p) != 0 ||
+                    PyList_Append(f_cnts.p, b.p) != 0)
+                    return false;
+                const Py_ssize_t ft = PyList_GET_SIZE(f_tasks.p);
+                if (PyList_SetSlice(f_tasks.p, ft, ft, sl.p) != 0)
+                    return false;
+            }
+        }
+        if (PyDict_SetItem(committed.p, key.p, job) != 0) return false;
+        if (want_fire) {
+            Ref ev(Py_BuildValue("(OnOOO)", s_f, c, f_nodes.p, f_cnts.p,
+                                 f_tasks.p));
+            if (!ev || PyList_Append(events.p, ev.p) != 0) return false;
+        }
+        ++n_committed;
+        return true;
+    }
+
+    bool revert(Py_ssize_t c, const vamd::SettleOut& so) {
+        if (so.n_rev == 0) return true;
+        Ref pairs(PyList_New(static_cast<Py_ssize_t>(so.n_rev)));
+        if (!pairs) return false;
+        for (size_t i = 0; i < so.n_rev; ++i) {
+            PyObject* t = Py_BuildValue("(ii)", so.rev_node[i], so.rev_cnt[i]);
+            if (t == nullptr) return false;
+            PyList_SET_ITEM(pairs.p, static_cast<Py_ssize_t>(i), t);
+        }
+        Ref ev(Py_BuildValue("(OnO)", s_r, c, pairs.p));
+        return ev && PyList_Append(events.p, ev.p) == 0;
+    }
+};
+
+bool settle_error(int st) {
+    switch (st) {
+    case vamd::SETTLE_OK:
+        return false;
+    case vamd::SETTLE_ERR_CAPACITY:
+        PyErr_SetString(PyExc_RuntimeError, "settle output capacity exceeded");
+        break;
+    case vamd::SETTLE_ERR_NEGATIVE:
+        PyErr_SetString(PyExc_ValueError, "negative count in placement log");
+        break;
+    default:
+        PyErr_SetString(PyExc_IndexError,
+                        "placement log names a node outside the lost mask");
+    }
+    return true;
+}
+
+bool attr_long(PyObject* o, PyObject* name, long* out) {
+    Ref v(PyObject_GetAttr(o, name));
+    if (!v) return false;
+    *out = PyLong_AsLong(v.p);
+    return !(*out == -1 && PyErr_Occurred());
+}
+
+// Mapping lookup: borrowed-free new reference, nullptr without an error
+// set when the key is absent.
+PyObject* map_get(PyObject* m, PyObject* key) {
+    if (PyDict_Check(m)) {
+        PyObject* v = PyDict_GetItemWithError(m, key);
+        Py_XINCREF(v);
+        return v;
+    }
+    PyObject* v = PyObject_GetItem(m, key);
+    if (v == nullptr && PyErr_ExceptionMatches(PyExc_KeyError)) PyErr_Clear();
+    return v;
+}
+
+PyObject* vec_bytes(const void* data, size_t nbytes) {
+    return PyBytes_FromStringAndSize(static_cast<const char*>(data),
+                                     static_cast<Py_ssize_t>(nbytes));
+}
+
+PyObject* apply_walk(PyObject*, PyObject* args) {
+    PyObject *classes, *jobs, *alias, *nodes, *o_jf, *o_cj, *o_ln, *o_lc,
+        *o_ll, *o_lost, *bound;
+    int want_fire;
+    if (!PyArg_ParseTuple(args, "OOOOOOOOOOOp", &classes, &jobs, &alias,
+                          &nodes, &o_jf, &o_cj, &o_ln, &o_lc, &o_ll, &o_lost,
+                          &bound, &want_fire))
+        return nullptr;
+    if (!PyList_Check(classes) || !PyList_Check(nodes)) {
+        PyErr_SetString(PyExc_TypeError, "classes and nodes must be lists");
+        return nullptr;
+    }
+    Buf jf, cj, ln, lc, ll, lost;
+    if (!jf.get(o_jf, 1, "job_flag") || !cj.get(o_cj, 4, "class_job") ||
+        !ln.get(o_ln, 4, "log_nodes") || !lc.get(o_lc, 4, "log_counts") ||
+        !ll.get(o_ll, 4, "log_len"))
+        return nullptr;
+    const uint8_t* lost_p = nullptr;
+    int64_t lost_n = 0;
+    if (o_lost != Py_None) {
+        if (!lost.get(o_lost, 1, "lost mask")) return nullptr;
+        lost_p = static_cast<const uint8_t*>(lost.v.buf);
+        lost_n = lost.count();
+    }
+    const Py_ssize_t C = PyList_GET_SIZE(classes);
+    const Py_ssize_t log_total = ln.count();
+    if (cj.count() < C || ll.count() < C || lc.count() != log_total) {
+        PyErr_SetString(PyExc_ValueError,
+                        "result arrays do not cover the plan's classes");
+        return nullptr;
+    }
+    const uint8_t* jf_p = static_cast<const uint8_t*>(jf.v.buf);
+    const int32_t* cj_p = static_cast<const int32_t*>(cj.v.buf);
+    const int32_t* ln_p = static_cast<const int32_t*>(ln.v.buf);
+    const int32_t* lc_p = static_cast<const int32_t*>(lc.v.buf);
+    const int32_t* ll_p = static_cast<const int32_t*>(ll.v.buf);
+    const Py_ssize_t n_jobs = jf.count();
+
+    GcPause gc_pause;
+    Walk w;
+    w.jobs = jobs;
+    w.alias = alias;
+    w.nodes = nodes;
+    w.bound = bound;
+    w.want_fire = want_fire != 0;
+    w.bind_by_job.reset(PyDict_New());
+    w.committed.reset(PyDict_New());
+    w.full.reset(PySet_New(nullptr));
+    w.events.reset(PyList_New(0));
+    if (!w.bind_by_job || !w.committed || !w.full || !w.events)
+        return nullptr;
+
+    std::vector<int32_t> p_entry, p_node, p_take, p_toff, rev_node, rev_cnt,
+        e_ntasks, e_min;
+    std::vector<uint8_t> outcome, full;
+
+    for (Py_ssize_t c = 0; c < C; ++c) {
+        const int32_t j = cj_p[c];
+        if (j < 0 || j >= n_jobs) {
+            PyErr_SetString(PyExc_IndexError, "class_job outside job_flag");
+            return nullptr;
+        }
+        if (!jf_p[j]) continue;
+        const int64_t n = ll_p[c];
+        if (n == 0) continue;
+        PyObject* cp = PyList_GET_ITEM(classes, c);
+        long off;
+        if (!attr_long(cp, s_log_off, &off)) return nullptr;
+        if (n < 0 || off < 0 || off + n > log_total) {
+            PyErr_SetString(PyExc_IndexError,
+                            "class log slice outside the log arrays");
+            return nullptr;
+        }
+        Ref bundle(PyObject_GetAttr(cp, s_bundle));
+        if (!bundle) return nullptr;
+        const bool plain = bundle.p == Py_None;
+        if (!plain && !PyList_Check(bundle.p)) {
+            PyErr_SetString(PyExc_TypeError, "bundle must be a list or None");
+            return nullptr;
+        }
+        const Py_ssize_t n_entries = plain ? 1 : PyList_GET_SIZE(bundle.p);
+        const size_t cap = static_cast<size_t>(n) +
+                           static_cast<size_t>(n_entries);
+        p_entry.resize(cap); p_node.resize(cap);
+        p_take.resize(cap); p_toff.resize(cap);
+        rev_node.resize(cap); rev_cnt.resize(cap);
+        outcome.resize(static_cast<size_t>(n_entries) + 1);
+        full.resize(static_cast<size_t>(n_entries) + 1);
+        vamd::SettleOut so{};
+        so.p_entry = p_entry.data(); so.p_node = p_node.data();
+        so.p_take = p_take.data(); so.p_toff = p_toff.data();
+        so.piece_cap = cap;
+        so.outcome = outcome.data(); so.full = full.data();
+        so.rev_node = rev_node.data(); so.rev_cnt = rev_cnt.data();
+        so.rev_cap = cap;
+
+        if (plain) {
+            Ref jkey(PyObject_GetAttr(cp, s_job_key));
+            if (!jkey) return nullptr;
+            Ref job(map_get(jobs, jkey.p));
+            if (!job && PyErr_Occurred()) return nullptr;
+            int truth = job ? PyObject_IsTrue(job.p) : 0;
+            if (truth < 0) return nullptr;
+            if (!truth) {
+                Ref real(PyObject_GetItem(alias, jkey.p));
+                if (!real) return nullptr;
+                job.reset(PyObject_GetItem(jobs, real.p));
+                if (!job) return nullptr;
+            }
+            if (settle_error(vamd::settle_plain(ln_p + off, lc_p + off, n,
+                                                lost_p, lost_n, &so)))
+                return nullptr;
+            if (so.outcome[0] == vamd::SETTLE_LOST) {
+                ++w.n_lost;
+                if (!w.revert(c, so)) return nullptr;
+            } else if (so.outcome[0] == vamd::SETTLE_COMMITTED) {
+                Ref tclass(PyObject_GetAttr(cp, s_tclass));
+                if (!tclass) return nullptr;
+                Ref tasks(PyObject_GetAttr(tclass.p, s_tasks));
+                if (!tasks) return nullptr;
+                if (!PyList_Check(tasks.p)) {
+                    PyErr_SetString(PyExc_TypeError, "tasks must be a list");
+                    return nullptr;
+                }
+                if (!w.commit(job.p, tasks.p, c, so, 0, so.n_pieces, true))
+                    return nullptr;
+            }
+            continue;
+        }
+
+        e_ntasks.resize(static_cast<size_t>(n_entries));
+        e_min.resize(static_cast<size_t>(n_entries));
+        for (Py_ssize_t b = 0; b < n_entries; ++b) {
+            PyObject* be = PyList_GET_ITEM(bundle.p, b);
+            long nt, mn;
+            if (!attr_long(be, s_ntasks, &nt) ||
+                !attr_long(be, s_min_needed, &mn))
+                return nullptr;
+            if (nt < INT32_MIN || nt > INT32_MAX || mn < INT32_MIN ||
+                mn > INT32_MAX) {
+                PyErr_SetString(PyExc_OverflowError, "bundle entry size");
+                return nullptr;
+            }
+            e_ntasks[b] = static_cast<int32_t>(nt);
+            e_min[b] = static_cast<int32_t>(mn);
+        }
+        if (settle_error(vamd::settle_bundle(ln_p + off, lc_p + off, n,
+                                             e_ntasks.data(), e_min.data(),
+                                             n_entries, lost_p, lost_n, &so)))
+            return nullptr;
+        size_t pp = 0;
+        for (Py_ssize_t b = 0; b < n_entries; ++b) {
+            const uint8_t oc = so.outcome[b];
+            if (oc == vamd::SETTLE_GANG_MISS) { ++w.n_missed; continue; }
+            if (oc == vamd::SETTLE_LOST) { ++w.n_lost; continue; }
+            if (oc != vamd::SETTLE_COMMITTED) continue;
+            size_t pe = pp;
+            while (pe < so.n_pieces && so.p_entry[pe] == b) ++pe;
+            PyObject* be = PyList_GET_ITEM(bundle.p, b);
+            Ref job(PyObject_GetAttr(be, s_job));
+            if (!job) return nullptr;
+            Ref jkey(PyObject_GetAttr(be, s_job_key));
+            if (!jkey) return nullptr;
+            if (job.p == Py_None) {
+                job.reset(PyObject_GetItem(jobs, jkey.p));
+                if (!job) return nullptr;
+            }
+            Ref tasks(PyObject_GetAttr(be, s_tasks));
+            if (!tasks) return nullptr;
+            if (!PyList_Check(tasks.p)) {
+                PyErr_SetString(PyExc_TypeError, "tasks must be a list");
+                return nullptr;
+            }
+            if (!w.commit(job.p, tasks.p, c, so, pp, pe, false))
+                return nullptr;
+            if (so.full[b] && PySet_Add(w.full.p, jkey.p) != 0)
+                return nullptr;
+            pp = pe;
+        }
+        w.n_tail += static_cast<long>(so.n_tail);
+        if (!w.revert(c, so)) return nullptr;
+    }
+
+    Ref rows(vec_bytes(w.acc_rows.data(), w.acc_rows.size() * 8));
+    Ref cnts(vec_bytes(w.acc_cnts.data(), w.acc_cnts.size() * 8));
+    Ref cls(vec_bytes(w.acc_cls.data(), w.acc_cls.size() * 8));
+    if (!rows || !cnts || !cls) return nullptr;
+    return Py_BuildValue("(OOOOOOO(llll))", rows.p, cnts.p, cls.p,
+                         w.bind_by_job.p, w.committed.p, w.full.p,
+                         w.events.p, w.n_committed, w.n_missed, w.n_lost,
+                         w.n_tail);
+}
+
+// JobInfo.finish_bind for every (key, tasks) of by_job, in one call: the
+// walk already stored BOUND on the tasks, only the status-bucket move and
+// the occupancy count remain.  Wholesale when the batch is the job's whole
+// pending bucket (the gang case).
+PyObject* finish_binds(PyObject*, PyObject* args) {
+    PyObject *by_job, *jobs, *pending, *bound;
+    if (!PyArg_ParseTuple(args, "O!OOO", &PyDict_Type, &by_job, &jobs,
+                          &pending, &bound))
+        return nullptr;
+    GcPause gc_pause;                  // one fresh bucket dict per job
+    Py_ssize_t pos = 0;
+    PyObject *key, *ts;
+    while (PyDict_Next(by_job, &pos, &key, &ts)) {
+        Ref job(map_get(jobs, key));
+        if (!job) {
+            if (PyErr_Occurred()) return nullptr;
+            continue;
+        }
+        if (job.p == Py_None) continue;
+        const Py_ssize_t n = PyObject_Length(ts);
+        if (n < 0) return nullptr;
+        Ref idx(PyObject_GetAttr(job.p, s_task_status_index));
+        if (!idx) return nullptr;
+        if (!PyDict_Check(idx.p)) {
+            PyErr_SetString(PyExc_TypeError,
+                            "task_status_index must be a dict");
+            return nullptr;
+        }
+        Ref src(PyDict_GetItemWithError(idx.p, pending));
+        if (!src && PyErr_Occurred()) return nullptr;
+        Py_XINCREF(src.p);
+        if (src && !PyDict_Check(src.p)) {
+            PyErr_SetString(PyExc_TypeError, "status bucket must be a dict");
+            return nullptr;
+        }
+        Ref dst(PyDict_GetItemWithError(idx.p, bound));
+        if (!dst && PyErr_Occurred()) return nullptr;
+        Py_XINCREF(dst.p);
+        if (dst && !PyDict_Check(dst.p)) {
+            PyErr_SetString(PyExc_TypeError, "status bucket must be a dict");
+            return nullptr;
+        }
+        if (src && PyDict_GET_SIZE(src.p) == n) {
+            if (dst && PyDict_GET_SIZE(dst.p) > 0) {
+                if (PyDict_Update(dst.p, src.p) != 0) return nullptr;
+            } else if (PyDict_SetItem(idx.p, bound, src.p) != 0) {
+                return nullptr;
+            }
+            Ref fresh(PyDict_New());
+            if (!fresh || PyDict_SetItem(idx.p, pending, fresh.p) != 0)
+                return nullptr;
+        } else {
+            if (!dst) {
+                dst.reset(PyDict_New());
+                if (!dst || PyDict_SetItem(idx.p, bound, dst.p) != 0)
+                    return nullptr;
+            }
+            Ref seq(PySequence_Fast(ts, "bind list must be a sequence"));
+            if (!seq) return nullptr;
+            for (Py_ssize_t i = 0; i < PySequence_Fast_GET_SIZE(seq.p); ++i) {
+                PyObject* t = PySequence_Fast_GET_ITEM(seq.p, i);
+                Ref tkey(PyObject_GetAttr(t, s_key));
+                if (!tkey) return nullptr;
+                if (src && PyDict_DelItem(src.p, tkey.p) != 0) {
+                    if (!PyErr_ExceptionMatches(PyExc_KeyError))
+                        return nullptr;
+                    PyErr_Clear();
+                }
+                if (PyDict_SetItem(dst.p, tkey.p, t) != 0) return nullptr;
+            }
+        }
+        Ref occ(PyObject_GetAttr(job.p, s_occ));
+        if (!occ) return nullptr;
+        Ref add(PyLong_FromSsize_t(n));
+        if (!add) return nullptr;
+        Ref sum(PyNumber_Add(occ.p, add.p));   // BOUND occupies, PENDING not
+        if (!sum || PyObject_SetAttr(job.p, s_occ, sum.p) != 0 ||
+            PyObject_SetAttr(job.p, s_alloc_vec, Py_None) != 0)
+            return nullptr;
+    }
+    Py_RETURN_NONE;
+}
+
+PyMethodDef methods[] = {
+    {"finish_binds", finish_binds, METH_VARARGS,
+     "finish_binds(by_job, jobs, pending, bound): JobInfo.finish_bind for "
+     "every job of by_job found in jobs"},
+    {"apply_walk", apply_walk, METH_VARARGS,
+     "apply_walk(classes, jobs, alias, nodes, job_flag, class_job, "
+     "log_nodes, log_counts, log_len, lost_mask, bound, want_fire) -> "
+     "(rows, counts, classes, bind_by_job, committed, full_keys, events, "
+     "(n_committed, n_gang_missed, n_lost, n_tail))"},
+    {nullptr, nullptr, 0, nullptr}};
+
+PyModuleDef moddef = {PyModuleDef_HEAD_INIT, "_vamd_host",
+                      "Host-native allocate apply walk.", -1, methods,
+                      nullptr, nullptr, nullptr, nullptr};
+
+}  // namespace
+
+PyMODINIT_FUNC PyInit__vamd_host(void) {
+    struct { PyObject** slot; const char* text; } names[] = {
+        {&s_bundle, "bundle"}, {&s_log_off, "log_off"},
+        {&s_job_key, "job_key"}, {&s_tclass, "tclass"}, {&s_tasks, "tasks"},
+        {&s_ntasks, "ntasks"}, {&s_min_needed, "min_needed"},
+        {&s_job, "job"}, {&s_key, "key"}, {&s_name, "name"},
+        {&s_batches, "_batches"}, {&s_node_name, "node_name"},
+        {&s_status, "status"}, {&s_f, "f"}, {&s_r, "r"},
+        {&s_task_status_index, "task_status_index"}, {&s_occ, "_occ"},
+        {&s_alloc_vec, "_alloc_vec"}};
+    for (auto& nm : names) {
+        *nm.slot = PyUnicode_InternFromString(nm.text);
+        if (*nm.slot == nullptr) return nullptr;
+    }
+    return PyModule_Create(&moddef);
+}

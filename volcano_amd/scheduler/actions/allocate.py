@@ -28,6 +28,7 @@ from ...api.types import PodGroupPhase, TaskStatus
 
 PENDING_S = TaskStatus.PENDING
 BOUND_S = TaskStatus.BOUND
+from ...ops import host
 from ...utils.metrics import METRICS
 from ..plan import (BundleEntry, ClassPlan, CyclePlan, JobPlan, run_plan_hip,
                     run_plan_torch)
@@ -719,19 +720,104 @@ class AllocateAction:
         resolution) lists node ids this rank LOST in the cross-rank
         reconcile: any job with a placement there is reverted wholesale
         (gang atomicity) and its device usage unwound."""
-        nt = ssn.node_tensors
         nodes_sorted = getattr(ssn.cache, "nodes_sorted", None)
         if nodes_sorted is None or len(nodes_sorted) != len(ssn.nodes):
             nodes_sorted = sorted(ssn.nodes.values(), key=lambda n: n.name)
         ledger = getattr(ssn.cache, "ledger", None)
 
+        # fire event handlers only when someone registered one — building
+        # the per-piece argument lists for nobody was measurable at 10k jobs
+        fire = ssn.fire_allocate if ssn.event_handlers else None
+        if plan.classes and host.native_apply_enabled():
+            walk = self._walk_native
+        else:
+            walk = self._walk_py
+        rows, cnts, acc_cls, bind_by_job, committed_jobs, full_keys = walk(
+            ssn, plan, result, bad_nodes, nodes_sorted, fire)
+
+        if len(rows):
+            vals = cnts[:, None] * plan.req_np[acc_cls].astype(np.float64)
+            if ledger is not None:
+                ledger.add_used_rows(rows, vals)
+            else:   # bare-cache tests: per-piece Resource math
+                for k in range(len(rows)):
+                    cp = plan.classes[acc_cls[k]]
+                    nodes_sorted[rows[k]]._acct(
+                        cp.tclass.request.clone().multi(float(cnts[k])),
+                        1, 0, 0)
+
+        if bind_by_job:
+            ssn.cache.bind_tasks(None, by_job=bind_by_job, preset=True)
+
+        # flip gang-ready podgroups to Running (job_updater analog) —
+        # walk the committed set directly (was a re-walk of every plan
+        # class/bundle entry)
+        alias = getattr(plan, "job_alias", {})
+        jr = ssn.job_ready_fns
+        fast_ready = len(jr) == 1 and getattr(jr[0], "is_gang", False)
+        running = PodGroupPhase.RUNNING.value
+        store = getattr(ssn.cache, "store", None)
+        seen = set()
+        for key, job in committed_jobs.items():
+            real = alias.get(key) if alias else None
+            if real is not None:
+                if real in seen:
+                    continue
+                seen.add(real)
+                job = ssn.jobs[real]
+            if fast_ready and key in full_keys:
+                ready = True        # whole gang placed this cycle
+            else:
+                ready = (job.is_ready() and job.roles_ready()) \
+                    if fast_ready else ssn.job_ready(job)
+            pg = job.podgroup
+            if ready and pg is not None and pg.status.phase != running:
+                pg.status.phase = running
+                if store is not None:
+                    ssn.cache.update_podgroup(job)
+
+    def _walk_native(self, ssn, plan: CyclePlan, result, bad_nodes,
+                     nodes_sorted, fire):
+        """The slot walk in native code (``_vamd_host.apply_walk``): one
+        call settles every class and does the per-task object updates.
+        Device-side reverts and event handlers run here, in walk order,
+        with the argument lists the Python walk would have built."""
+        lost = None
+        if bad_nodes:
+            lost = np.zeros(len(nodes_sorted), dtype=np.uint8)
+            lost[[b for b in bad_nodes if 0 <= b < len(lost)]] = 1
+        i32 = np.int32
+        (rows, cnts, acc_cls, bind_by_job, committed_jobs, full_keys,
+         events, stats) = host.load().apply_walk(
+            plan.classes, ssn.jobs, getattr(plan, "job_alias", {}),
+            nodes_sorted if type(nodes_sorted) is list
+            else list(nodes_sorted),
+            np.ascontiguousarray(result.job_flag, dtype=np.uint8),
+            np.ascontiguousarray(plan.class_job, dtype=i32),
+            np.ascontiguousarray(result.log_nodes, dtype=i32),
+            np.ascontiguousarray(result.log_counts, dtype=i32),
+            np.ascontiguousarray(result.log_len, dtype=i32),
+            lost, BOUND_S, fire is not None)
+        self.last_walk_stats = stats
+        for ev in events:
+            cp = plan.classes[ev[1]]
+            if ev[0] == "r":
+                self._revert_pieces(plan, cp, ev[2])
+            else:
+                fire(cp.tclass, ev[2], ev[3], ev[4])
+        return (np.frombuffer(rows, dtype=np.int64),
+                np.frombuffer(cnts, dtype=np.float64),
+                np.frombuffer(acc_cls, dtype=np.int64),
+                bind_by_job, committed_jobs, full_keys)
+
+    def _walk_py(self, ssn, plan: CyclePlan, result, bad_nodes,
+                 nodes_sorted, fire):
+        """The slot walk interpreted in Python — the oracle for the native
+        walk and the fallback when the extension is off or unavailable."""
         bind_by_job: Dict[str, List] = {}
         committed_jobs: Dict[str, object] = {}     # key -> JobInfo
         full_keys = set()       # jobs whose ENTIRE task set placed —
         # gang-ready by construction, no is_ready() walk needed
-        # fire event handlers only when someone registered one — building
-        # the per-piece argument lists for nobody was measurable at 10k jobs
-        fire = ssn.fire_allocate if ssn.event_handlers else None
         jf = result.job_flag
         cls_job = plan.class_job
         ln_all = result.log_nodes
@@ -853,49 +939,10 @@ class AllocateAction:
                 if reverted:
                     self._revert_pieces(plan, cp, reverted)
 
-        if acc_rows:
-            rows = np.asarray(acc_rows, dtype=np.int64)
-            cnts = np.asarray(acc_cnts, dtype=np.float64)
-            vals = cnts[:, None] * plan.req_np[
-                np.asarray(acc_cls, dtype=np.int64)].astype(np.float64)
-            if ledger is not None:
-                ledger.add_used_rows(rows, vals)
-            else:   # bare-cache tests: per-piece Resource math
-                for k in range(len(acc_rows)):
-                    cp = plan.classes[acc_cls[k]]
-                    nodes_sorted[acc_rows[k]]._acct(
-                        cp.tclass.request.clone().multi(float(acc_cnts[k])),
-                        1, 0, 0)
-
-        if bind_by_job:
-            ssn.cache.bind_tasks(None, by_job=bind_by_job, preset=True)
-
-        # flip gang-ready podgroups to Running (job_updater analog) —
-        # walk the committed set directly (was a re-walk of every plan
-        # class/bundle entry)
-        alias = getattr(plan, "job_alias", {})
-        jr = ssn.job_ready_fns
-        fast_ready = len(jr) == 1 and getattr(jr[0], "is_gang", False)
-        running = PodGroupPhase.RUNNING.value
-        store = getattr(ssn.cache, "store", None)
-        seen = set()
-        for key, job in committed_jobs.items():
-            real = alias.get(key)
-            if real is not None:
-                if real in seen:
-                    continue
-                seen.add(real)
-                job = ssn.jobs[real]
-            if fast_ready and key in full_keys:
-                ready = True        # whole gang placed this cycle
-            else:
-                ready = (job.is_ready() and job.roles_ready()) \
-                    if fast_ready else ssn.job_ready(job)
-            pg = job.podgroup
-            if ready and pg is not None and pg.status.phase != running:
-                pg.status.phase = running
-                if store is not None:
-                    ssn.cache.update_podgroup(job)
+        return (np.asarray(acc_rows, dtype=np.int64),
+                np.asarray(acc_cnts, dtype=np.float64),
+                np.asarray(acc_cls, dtype=np.int64),
+                bind_by_job, committed_jobs, full_keys)
 
     @staticmethod
     def _revert_pieces(plan: CyclePlan, cp, pieces) -> None:

@@ -31,6 +31,12 @@ class Binder:
     def bind(self, tasks: List[TaskInfo]) -> None:  # pragma: no cover
         raise NotImplementedError
 
+    def bind_batches(self, batches) -> None:
+        """Bind several task lists (one per job) in order.  Binders with a
+        cheaper bulk intake override this."""
+        for ts in batches:
+            self.bind(ts)
+
     def evict(self, task: TaskInfo, reason: str = "") -> None:  # pragma: no cover
         raise NotImplementedError
 
@@ -63,6 +69,11 @@ class FakeBinder(Binder):
     def bind(self, tasks: List[TaskInfo]) -> None:
         self._spans.append(tasks)
         self.bound_count += len(tasks)
+
+    def bind_batches(self, batches) -> None:
+        batches = list(batches)
+        self._spans.extend(batches)
+        self.bound_count += sum(map(len, batches))
 
     def clear(self) -> None:
         self._binds.clear()
@@ -440,8 +451,12 @@ class SchedulerCache:
                 for ts in by_job.values():
                     self._task_node.update((t.key, t.node_name)
                                            for t in ts)
-            for ts in by_job.values():
-                self.binder.bind(ts)
+            batches = getattr(self.binder, "bind_batches", None)
+            if batches is not None:
+                batches(by_job.values())
+            else:   # duck-typed binders that only know bind()
+                for ts in by_job.values():
+                    self.binder.bind(ts)
         else:
             if self._watch is not None:
                 # incarnation bookkeeping only matters when store events flow
@@ -449,7 +464,13 @@ class SchedulerCache:
             self.binder.bind(tasks)
         # ``preset``: the caller's task walk already wrote BOUND statuses
         # (allocate._apply fuses it with the node_name pass); only the
-        # bucket move remains
+        # bucket move remains — in native code when the host extension is on
+        if preset:
+            from ..ops import host
+            if host.native_apply_enabled():
+                host.load().finish_binds(by_job, self.jobs,
+                                         TaskStatus.PENDING, TaskStatus.BOUND)
+                return
         for key, ts in by_job.items():
             job = self.jobs.get(key)
             if job is not None:
