@@ -6,12 +6,18 @@
 // binder and pod-group updates stay in Python and get their arguments
 // back from here in walk order.
 //
+// The other per-job loops of a cycle live here too: the JobTable column
+// scan (scan_jobs), the fused-run bundle entries of the plan builder
+// (bundle_entries) and the bulk pod-group phase store
+// (set_podgroup_phase).  Each has its Python loop as oracle and fallback.
+//
 // Host-only C++ (no HIP); not linked against libpython.
 #define PY_SSIZE_T_CLEAN
 #include <Python.h>
 #include <structmember.h>
 
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "settle_core.h"
@@ -29,16 +35,38 @@ struct Ref {                       // owning reference, released on scope exit
     void reset(PyObject* o) { Py_XDECREF(p); p = o; }
 };
 
-struct Buf {                       // contiguous read-only buffer view
+struct Buf {                       // contiguous buffer view
     Py_buffer v;
     bool held = false;
     ~Buf() { if (held) PyBuffer_Release(&v); }
-    bool get(PyObject* o, Py_ssize_t itemsize, const char* what) {
-        if (PyObject_GetBuffer(o, &v, PyBUF_C_CONTIGUOUS) != 0) return false;
+    bool get(PyObject* o, Py_ssize_t itemsize, const char* what,
+             int flags = PyBUF_C_CONTIGUOUS) {
+        if (PyObject_GetBuffer(o, &v, flags) != 0) return false;
         held = true;
         if (v.itemsize != itemsize) {
             PyErr_Format(PyExc_TypeError, "%s: expected itemsize %zd, got %zd",
                          what, itemsize, v.itemsize);
+            return false;
+        }
+        return true;
+    }
+    // A writable integer column of exactly `n` items.
+    bool get_column(PyObject* o, Py_ssize_t itemsize, Py_ssize_t n,
+                    const char* what, bool writable) {
+        int flags = PyBUF_C_CONTIGUOUS | PyBUF_FORMAT;
+        if (writable) flags |= PyBUF_WRITABLE;
+        if (!get(o, itemsize, what, flags)) return false;
+        const char* f = v.format ? v.format : "b";
+        if (*f == '<' || *f == '=' || *f == '@') ++f;
+        if (f[0] == '\0' || f[1] != '\0' ||
+            std::strchr("bBhHiIlLqQnN", f[0]) == nullptr) {
+            PyErr_Format(PyExc_TypeError, "%s: expected an integer column",
+                         what);
+            return false;
+        }
+        if (count() != n) {
+            PyErr_Format(PyExc_ValueError, "%s: expected %zd rows, got %zd",
+                         what, n, count());
             return false;
         }
         return true;
@@ -48,7 +76,8 @@ struct Buf {                       // contiguous read-only buffer view
 
 PyObject *s_bundle, *s_log_off, *s_job_key, *s_tclass, *s_tasks, *s_ntasks,
     *s_min_needed, *s_job, *s_key, *s_name, *s_batches, *s_node_name,
-    *s_status, *s_f, *s_r, *s_task_status_index, *s_occ, *s_alloc_vec;
+    *s_status, *s_f, *s_r, *s_task_status_index, *s_occ, *s_alloc_vec,
+    *s_podgroup, *s_phase, *s_tver, *s_gated, *s_job_gated, *s_values;
 
 // Offset of a plain object-valued __slots__ member of `tp`, or -1 when
 // `name` is anything else (property, instance-dict attribute, read-only
@@ -117,6 +146,15 @@ struct GcPause {
 #endif
 };
 
+// Lists created here that hold only task objects leave the collector's
+// sight right after creation.  A TaskInfo is slotted and what it reaches
+// (strings, numbers, its Resource, its Pod manifest) never refers back to
+// a scheduler-side list, so such a list cannot sit on a reference cycle:
+// it dies by reference count, and the collector no longer walks 100k task
+// pointers per young-generation pass (the catch-up bill that used to
+// arrive right after the GcPause below ended).
+inline void untrack_task_list(PyObject* list) { PyObject_GC_UnTrack(list); }
+
 struct Walk {
     TaskStore tstore;
     PyObject* jobs;
@@ -141,8 +179,11 @@ struct Walk {
             Ref fresh(PyList_New(0));
             if (!fresh || PyDict_SetItem(bind_by_job.p, key.p, fresh.p) != 0)
                 return false;
+            untrack_task_list(fresh.p);
             jl = fresh.p;          // the dict keeps it alive
         }
+        // the handler argument lists stay tracked: plugin code may store
+        // anything in them
         Ref f_nodes, f_cnts, f_tasks;
         if (want_fire) {
             f_nodes.reset(PyList_New(0));
@@ -167,6 +208,7 @@ struct Walk {
             Ref sl(PyList_GetSlice(tasks, toff,
                                    static_cast<Py_ssize_t>(toff) + take));
             if (!sl) return false;
+            untrack_task_list(sl.p);
             const Py_ssize_t k = PyList_GET_SIZE(sl.p);
             if (exact && k != take) {
                 PyErr_SetString(PyExc_RuntimeError,
@@ -541,7 +583,369 @@ PyObject* finish_binds(PyObject*, PyObject* args) {
     Py_RETURN_NONE;
 }
 
+// ---- per-job loops of a cycle --------------------------------------------
+
+// One attribute of the objects of one type.  The type seen first gets the
+// slot offset resolved once per module; its instances are then read and
+// written in place.  Every other object (and every non-slot attribute)
+// goes through PyObject_GetAttr / PyObject_SetAttr.
+struct SlotAttr {
+    PyObject** name;               // interned at module init
+    PyTypeObject* type = nullptr;  // strong, kept for the module's life
+    Py_ssize_t off = -1;
+
+    explicit SlotAttr(PyObject** n) : name(n) {}
+
+    PyObject** slot(PyObject* o) {
+        if (type == nullptr) {
+            type = Py_TYPE(o);
+            Py_INCREF(type);
+            off = slot_offset(type, *name);
+        }
+        if (Py_TYPE(o) != type || off < 0) return nullptr;
+        return reinterpret_cast<PyObject**>(reinterpret_cast<char*>(o) + off);
+    }
+    PyObject* get(PyObject* o) {   // new reference
+        PyObject** s = slot(o);
+        if (s != nullptr && *s != nullptr) {
+            Py_INCREF(*s);
+            return *s;
+        }
+        return PyObject_GetAttr(o, *name);   // raises for an empty slot
+    }
+    bool set(PyObject* o, PyObject* v) {
+        PyObject** s = slot(o);
+        if (s == nullptr) return PyObject_SetAttr(o, *name, v) == 0;
+        PyObject* old = *s;
+        Py_INCREF(v);
+        *s = v;
+        Py_XDECREF(old);
+        return true;
+    }
+};
+
+SlotAttr a_job_idx(&s_task_status_index), a_job_occ(&s_occ),
+    a_job_pg(&s_podgroup), a_job_tver(&s_tver), a_job_key(&s_key),
+    a_pg_status(&s_status), a_st_phase(&s_phase), a_task_gated(&s_gated);
+
+// getattr(o, name, <absent>): 1 found (new reference in *out), 0 absent,
+// -1 error.
+int optional_attr(PyObject* o, PyObject* name, PyObject** out) {
+#if PY_VERSION_HEX >= 0x030D0000
+    return PyObject_GetOptionalAttr(o, name, out);
+#else
+    return _PyObject_LookupAttr(o, name, out);
+#endif
+}
+
+// `len(b) if b else 0` for the status bucket `key` of a job's index.
+bool bucket_len(PyObject* idx, PyObject* key, int64_t* out) {
+    Ref b(map_get(idx, key));
+    *out = 0;
+    if (!b) return !PyErr_Occurred();
+    if (PyDict_Check(b.p)) {
+        *out = PyDict_GET_SIZE(b.p);
+        return true;
+    }
+    const int truth = PyObject_IsTrue(b.p);
+    if (truth < 0) return false;
+    if (truth) {
+        const Py_ssize_t n = PyObject_Length(b.p);
+        if (n < 0) return false;
+        *out = n;
+    }
+    return true;
+}
+
+bool as_i64(PyObject* v, int64_t* out) {
+    const long long x = PyLong_AsLongLong(v);
+    if (x == -1 && PyErr_Occurred()) return false;
+    *out = x;
+    return true;
+}
+
+// JobTable's per-cycle pass over the jobs: fills the dynamic columns and
+// returns the rows whose static-shape version moved.
+PyObject* scan_jobs(PyObject*, PyObject* args) {
+    PyObject *jobs, *pending, *failed, *pmap, *o_vers, *o_occ, *o_npend,
+        *o_nfailed, *o_phase;
+    int ph_pending, ph_other;
+    if (!PyArg_ParseTuple(args, "O!OOO!iiOOOOO", &PyList_Type, &jobs,
+                          &pending, &failed, &PyDict_Type, &pmap, &ph_pending,
+                          &ph_other, &o_vers, &o_occ, &o_npend, &o_nfailed,
+                          &o_phase))
+        return nullptr;
+    const Py_ssize_t J = PyList_GET_SIZE(jobs);
+    Buf vers, occ, npend, nfailed, phase;
+    if (!vers.get_column(o_vers, 8, J, "vers", false) ||
+        !occ.get_column(o_occ, 8, J, "occ", true) ||
+        !npend.get_column(o_npend, 8, J, "npend", true) ||
+        !nfailed.get_column(o_nfailed, 8, J, "nfailed", true) ||
+        !phase.get_column(o_phase, 1, J, "phase", true))
+        return nullptr;
+    if (ph_pending < INT8_MIN || ph_pending > INT8_MAX ||
+        ph_other < INT8_MIN || ph_other > INT8_MAX) {
+        PyErr_SetString(PyExc_OverflowError, "phase code outside int8");
+        return nullptr;
+    }
+    const int64_t* vers_p = static_cast<const int64_t*>(vers.v.buf);
+    int64_t* occ_p = static_cast<int64_t*>(occ.v.buf);
+    int64_t* npend_p = static_cast<int64_t*>(npend.v.buf);
+    int64_t* nfailed_p = static_cast<int64_t*>(nfailed.v.buf);
+    int8_t* phase_p = static_cast<int8_t*>(phase.v.buf);
+
+    Ref dirty(PyList_New(0));
+    if (!dirty) return nullptr;
+    for (Py_ssize_t k = 0; k < J; ++k) {
+        if (PyList_GET_SIZE(jobs) != J) {   // an attribute hook resized it
+            PyErr_SetString(PyExc_RuntimeError, "job list changed size");
+            return nullptr;
+        }
+        Ref job(PyList_GET_ITEM(jobs, k));
+        Py_INCREF(job.p);
+        Ref v(a_job_occ.get(job.p));
+        if (!v || !as_i64(v.p, &occ_p[k])) return nullptr;
+        Ref idx(a_job_idx.get(job.p));
+        if (!idx || !bucket_len(idx.p, pending, &npend_p[k]) ||
+            !bucket_len(idx.p, failed, &nfailed_p[k]))
+            return nullptr;
+        Ref pg(a_job_pg.get(job.p));
+        if (!pg) return nullptr;
+        long code = ph_pending;
+        if (pg.p != Py_None) {
+            Ref st(a_pg_status.get(pg.p));
+            if (!st) return nullptr;
+            Ref ph(a_st_phase.get(st.p));
+            if (!ph) return nullptr;
+            PyObject* c = PyDict_GetItemWithError(pmap, ph.p);   // borrowed
+            if (c == nullptr) {
+                if (PyErr_Occurred()) return nullptr;
+                code = ph_other;
+            } else {
+                code = PyLong_AsLong(c);
+                if (code == -1 && PyErr_Occurred()) return nullptr;
+                if (code < INT8_MIN || code > INT8_MAX) {
+                    PyErr_SetString(PyExc_OverflowError,
+                                    "phase code outside int8");
+                    return nullptr;
+                }
+            }
+        }
+        phase_p[k] = static_cast<int8_t>(code);
+        int64_t tver;
+        v.reset(a_job_tver.get(job.p));
+        if (!v || !as_i64(v.p, &tver)) return nullptr;
+        if (tver != vers_p[k]) {
+            Ref row(PyLong_FromSsize_t(k));
+            if (!row || PyList_Append(dirty.p, row.p) != 0) return nullptr;
+        }
+    }
+    return dirty.release();
+}
+
+// The five slots of the plan's BundleEntry type, resolved once per type
+// object.  `direct` holds when every one is a plain object slot of exactly
+// that type, so an instance can be made by tp_alloc plus five stores.
+struct EntryType {
+    PyTypeObject* type = nullptr;  // strong
+    Py_ssize_t off[5] = {-1, -1, -1, -1, -1};
+    bool direct = false;
+
+    void resolve(PyTypeObject* tp) {
+        if (tp == type) return;
+        Py_INCREF(tp);
+        Py_XDECREF(type);
+        type = tp;
+        PyObject* names[5] = {s_job_key, s_tasks, s_ntasks, s_min_needed,
+                              s_job};
+        direct = (tp->tp_flags & Py_TPFLAGS_HEAPTYPE) != 0 &&
+                 (tp->tp_flags & Py_TPFLAGS_IS_ABSTRACT) == 0 &&
+                 tp->tp_alloc != nullptr && tp->tp_itemsize == 0;
+        for (int i = 0; i < 5; ++i) {
+            off[i] = slot_offset(tp, names[i]);
+            if (off[i] < 0 ||
+                off[i] + static_cast<Py_ssize_t>(sizeof(PyObject*)) >
+                    tp->tp_basicsize)
+                direct = false;
+        }
+    }
+
+    // Steals nothing; returns a new entry.
+    PyObject* make(PyObject* key, PyObject* tasks, PyObject* ntasks,
+                   PyObject* min_needed, PyObject* job) {
+        if (!direct)
+            return PyObject_CallFunctionObjArgs(
+                reinterpret_cast<PyObject*>(type), key, tasks, ntasks,
+                min_needed, job, nullptr);
+        PyObject* e = type->tp_alloc(type, 0);   // zeroed slots
+        if (e == nullptr) return nullptr;
+        PyObject* vals[5] = {key, tasks, ntasks, min_needed, job};
+        for (int i = 0; i < 5; ++i) {
+            Py_INCREF(vals[i]);
+            *reinterpret_cast<PyObject**>(reinterpret_cast<char*>(e) +
+                                          off[i]) = vals[i];
+        }
+        return e;
+    }
+};
+
+EntryType entry_type;
+
+// The values of a pending bucket as a fresh list, or nullptr with *skip
+// set when the job has nothing to plan (empty bucket, or a gated head).
+PyObject* pending_tasks(PyObject* pend, bool* skip) {
+    *skip = false;
+    Ref tasks;
+    if (PyDict_CheckExact(pend)) {
+        const Py_ssize_t n = PyDict_GET_SIZE(pend);
+        if (n == 0) { *skip = true; return nullptr; }
+        tasks.reset(PyList_New(n));
+        if (!tasks) return nullptr;
+        Py_ssize_t pos = 0, at = 0;
+        PyObject* t;
+        while (at < n && PyDict_Next(pend, &pos, nullptr, &t)) {
+            Py_INCREF(t);
+            PyList_SET_ITEM(tasks.p, at++, t);
+        }
+        if (at != n) {
+            PyErr_SetString(PyExc_RuntimeError, "pending bucket changed size");
+            return nullptr;
+        }
+    } else {
+        const int truth = PyObject_IsTrue(pend);
+        if (truth < 0) return nullptr;
+        if (!truth) { *skip = true; return nullptr; }
+        Ref vals(PyObject_CallMethodObjArgs(pend, s_values, nullptr));
+        if (!vals) return nullptr;
+        tasks.reset(PySequence_List(vals.p));
+        if (!tasks) return nullptr;
+        if (PyList_GET_SIZE(tasks.p) == 0) { *skip = true; return nullptr; }
+    }
+    // see untrack_task_list: the list holds tasks only.  Done before the
+    // gated read below, which may run Python code for a foreign task type.
+    untrack_task_list(tasks.p);
+    Ref first(PyList_GET_ITEM(tasks.p, 0));
+    Py_INCREF(first.p);
+    Ref gated(a_task_gated.get(first.p));
+    if (!gated) return nullptr;
+    const int g = PyObject_IsTrue(gated.p);
+    if (g < 0) return nullptr;
+    if (g) { *skip = true; return nullptr; }
+    return tasks.release();
+}
+
+// The bundle entries of one fused run jobs_l[i:j] of the plan builder.
+PyObject* bundle_entries(PyObject*, PyObject* args) {
+    PyObject *jobs_l, *gm_l, *pending, *etype;
+    Py_ssize_t i, j;
+    if (!PyArg_ParseTuple(args, "O!nnO!OO!", &PyList_Type, &jobs_l, &i, &j,
+                          &PyList_Type, &gm_l, &pending, &PyType_Type,
+                          &etype))
+        return nullptr;
+    if (i < 0 || j < i || j > PyList_GET_SIZE(jobs_l) ||
+        j > PyList_GET_SIZE(gm_l)) {
+        PyErr_SetString(PyExc_IndexError, "run outside the worksheet");
+        return nullptr;
+    }
+    entry_type.resolve(reinterpret_cast<PyTypeObject*>(etype));
+    GcPause gc_pause;              // one entry and one list per job
+    Ref entries(PyList_New(0));
+    if (!entries) return nullptr;
+    long long total = 0, mn = 1LL << 60;
+    for (Py_ssize_t k = i; k < j; ++k) {
+        if (k >= PyList_GET_SIZE(jobs_l) || k >= PyList_GET_SIZE(gm_l)) {
+            PyErr_SetString(PyExc_RuntimeError, "worksheet changed size");
+            return nullptr;
+        }
+        Ref jb(PyList_GET_ITEM(jobs_l, k));
+        Py_INCREF(jb.p);
+        Ref gm(PyList_GET_ITEM(gm_l, k));
+        Py_INCREF(gm.p);
+        Ref idx(a_job_idx.get(jb.p));
+        if (!idx) return nullptr;
+        Ref pend(map_get(idx.p, pending));
+        if (!pend) {
+            if (PyErr_Occurred()) return nullptr;
+            continue;
+        }
+        if (pend.p == Py_None) continue;
+        bool skip;
+        Ref tasks(pending_tasks(pend.p, &skip));
+        if (!tasks) {
+            if (skip) continue;
+            return nullptr;
+        }
+        const Py_ssize_t n = PyList_GET_SIZE(tasks.p);
+        int64_t g;
+        if (!as_i64(gm.p, &g)) return nullptr;
+        Ref key(a_job_key.get(jb.p));
+        if (!key) return nullptr;
+        Ref nt(PyLong_FromSsize_t(n));
+        if (!nt) return nullptr;
+        Ref e(entry_type.make(key.p, tasks.p, nt.p, gm.p, jb.p));
+        if (!e || PyList_Append(entries.p, e.p) != 0) return nullptr;
+        total += n;
+        if (g < mn) mn = g;
+    }
+    return Py_BuildValue("(OLL)", entries.p, total, mn);
+}
+
+// job.podgroup.status.phase = phase for every job with a pod group.
+// Returns (changed, gated): the jobs whose phase was another value, and,
+// when asked for, the jobs with a truthy `_gated` count.
+PyObject* set_podgroup_phase(PyObject*, PyObject* args) {
+    PyObject *jobs, *phase;
+    int want_gated = 0;
+    if (!PyArg_ParseTuple(args, "O!O|p", &PyList_Type, &jobs, &phase,
+                          &want_gated))
+        return nullptr;
+    Ref changed(PyList_New(0)), gated(PyList_New(0));
+    if (!changed || !gated) return nullptr;
+    for (Py_ssize_t k = 0; k < PyList_GET_SIZE(jobs); ++k) {
+        Ref job(PyList_GET_ITEM(jobs, k));
+        Py_INCREF(job.p);
+        Ref pg(a_job_pg.get(job.p));
+        if (!pg) return nullptr;
+        if (pg.p != Py_None) {
+            Ref st(a_pg_status.get(pg.p));
+            if (!st) return nullptr;
+            Ref cur(a_st_phase.get(st.p));
+            if (!cur) return nullptr;
+            const int ne = cur.p == phase
+                ? 0 : PyObject_RichCompareBool(cur.p, phase, Py_NE);
+            if (ne < 0) return nullptr;
+            if (ne) {
+                if (!a_st_phase.set(st.p, phase) ||
+                    PyList_Append(changed.p, job.p) != 0)
+                    return nullptr;
+            }
+        }
+        if (want_gated) {
+            PyObject* raw = nullptr;
+            const int have = optional_attr(job.p, s_job_gated, &raw);
+            if (have < 0) return nullptr;
+            if (have) {
+                Ref g(raw);
+                const int truth = PyObject_IsTrue(g.p);
+                if (truth < 0) return nullptr;
+                if (truth && PyList_Append(gated.p, job.p) != 0)
+                    return nullptr;
+            }
+        }
+    }
+    return Py_BuildValue("(OO)", changed.p, gated.p);
+}
+
 PyMethodDef methods[] = {
+    {"scan_jobs", scan_jobs, METH_VARARGS,
+     "scan_jobs(jobs, PENDING, FAILED, phase_map, ph_pending, ph_other, "
+     "vers, occ, npend, nfailed, phase) -> dirty rows; fills the four "
+     "columns"},
+    {"bundle_entries", bundle_entries, METH_VARARGS,
+     "bundle_entries(jobs_l, i, j, gm_l, PENDING, BundleEntry) -> "
+     "(entries, total, min_gang)"},
+    {"set_podgroup_phase", set_podgroup_phase, METH_VARARGS,
+     "set_podgroup_phase(jobs, phase, want_gated=False) -> (changed, gated)"},
     {"finish_binds", finish_binds, METH_VARARGS,
      "finish_binds(by_job, jobs, pending, bound): JobInfo.finish_bind for "
      "every job of by_job found in jobs"},
@@ -553,7 +957,8 @@ PyMethodDef methods[] = {
     {nullptr, nullptr, 0, nullptr}};
 
 PyModuleDef moddef = {PyModuleDef_HEAD_INIT, "_vamd_host",
-                      "Host-native allocate apply walk.", -1, methods,
+                      "Host-native per-job loops of a scheduling cycle.", -1,
+                      methods,
                       nullptr, nullptr, nullptr, nullptr};
 
 }  // namespace
@@ -567,7 +972,9 @@ PyMODINIT_FUNC PyInit__vamd_host(void) {
         {&s_batches, "_batches"}, {&s_node_name, "node_name"},
         {&s_status, "status"}, {&s_f, "f"}, {&s_r, "r"},
         {&s_task_status_index, "task_status_index"}, {&s_occ, "_occ"},
-        {&s_alloc_vec, "_alloc_vec"}};
+        {&s_alloc_vec, "_alloc_vec"}, {&s_podgroup, "podgroup"},
+        {&s_phase, "phase"}, {&s_tver, "_tver"}, {&s_gated, "gated"},
+        {&s_job_gated, "_gated"}, {&s_values, "values"}};
     for (auto& nm : names) {
         *nm.slot = PyUnicode_InternFromString(nm.text);
         if (*nm.slot == nullptr) return nullptr;

@@ -1,4 +1,5 @@
-"""Loader for the host-native apply walk (``_vamd_host`` CPython extension).
+"""Loader for the host-native per-job loops (``_vamd_host`` CPython
+extension).
 
 ``AllocateAction._apply`` hands the cycle readback to
 ``_vamd_host.apply_walk`` instead of interpreting the slot walk in Python.
@@ -8,6 +9,11 @@ The Python walk stays as the oracle and the fallback:
 * a failed import makes ONE build attempt, then falls back with a single
   logged warning.  ``native_apply_loaded()`` tells callers which path is
   live so a lost speed-up cannot hide (``smoke()`` asserts it).
+
+The other per-job loops of a cycle (JobTable column scan, fused-run
+bundle entries, bulk pod-group phase stores) follow the same scheme under
+their own switch, ``VAMD_NATIVE_JOBS=0``; ``native_jobs_enabled()`` is the
+per-cycle test and is also false for a stale module without them.
 """
 
 from __future__ import annotations
@@ -58,3 +64,20 @@ def native_apply_enabled() -> bool:
     if os.environ.get("VAMD_NATIVE_APPLY", "1") == "0":
         return False
     return load() is not None
+
+
+_JOBS_FUNCS = ("scan_jobs", "bundle_entries", "set_podgroup_phase")
+
+
+def native_jobs_enabled() -> bool:
+    """Per-cycle switch for the per-job loops: on unless VAMD_NATIVE_JOBS=0,
+    the module is unavailable, or it predates these functions."""
+    if os.environ.get("VAMD_NATIVE_JOBS", "1") == "0":
+        return False
+    mod = load()
+    if mod is None:
+        return False
+    for name in _JOBS_FUNCS:
+        if not hasattr(mod, name):
+            return False
+    return True

@@ -220,6 +220,9 @@ class AllocateAction:
         w_most = w.get("most", 0.0)
         w_bal = w.get("bal", 0.0)
         bias_fns = ssn.class_bias_fns
+        # the per-job loop of a fused run, in the host extension
+        run_entries = host.load().bundle_entries \
+            if host.native_jobs_enabled() else self._run_entries_py
 
         def class_bias(tc, job):
             out = None
@@ -289,23 +292,8 @@ class AllocateAction:
                     if got is None:
                         continue  # asks for a resource no node offers
                     req, tol, require, forbid = got
-                    entries: List[BundleEntry] = []
-                    total = 0
-                    mn = 1 << 60
-                    for k in range(i, j):
-                        jb = jobs_l[k]
-                        pend = jb.task_status_index.get(_TS.PENDING)
-                        if not pend:
-                            continue
-                        if next(iter(pend.values())).gated:
-                            continue
-                        tasks = list(pend.values())
-                        gm = gm_l[k]
-                        entries.append(BundleEntry(jb.key, tasks,
-                                                   len(tasks), gm, jb))
-                        total += len(tasks)
-                        if gm < mn:
-                            mn = gm
+                    entries, total, mn = run_entries(
+                        jobs_l, i, j, gm_l, PENDING_S, BundleEntry)
                     if not entries:
                         continue
                     close_bundle()
@@ -709,6 +697,29 @@ class AllocateAction:
         return True
 
     @staticmethod
+    def _run_entries_py(jobs_l, i, j, gm_l, pending, entry_type):
+        """Bundle entries of the fused run ``jobs_l[i:j]`` — the oracle for
+        ``_vamd_host.bundle_entries`` and the fallback when the extension
+        is off or unavailable."""
+        entries: List[BundleEntry] = []
+        total = 0
+        mn = 1 << 60
+        for k in range(i, j):
+            jb = jobs_l[k]
+            pend = jb.task_status_index.get(pending)
+            if not pend:
+                continue
+            if next(iter(pend.values())).gated:
+                continue
+            tasks = list(pend.values())
+            gm = gm_l[k]
+            entries.append(entry_type(jb.key, tasks, len(tasks), gm, jb))
+            total += len(tasks)
+            if gm < mn:
+                mn = gm
+        return entries, total, mn
+
+    @staticmethod
     def _clear_nominations(tasks) -> None:
         for t in tasks:
             t.nominated_node = ""
@@ -757,8 +768,34 @@ class AllocateAction:
         fast_ready = len(jr) == 1 and getattr(jr[0], "is_gang", False)
         running = PodGroupPhase.RUNNING.value
         store = getattr(ssn.cache, "store", None)
+        flipped = ()
+        if fast_ready and not alias and committed_jobs and \
+                host.native_jobs_enabled():
+            # jobs whose whole gang placed this cycle are ready by
+            # construction: one native call stores their phase; the loop
+            # below keeps the rest.  The store sees its updates in walk
+            # order either way.
+            if len(full_keys) == len(committed_jobs):
+                full_jobs, rest = list(committed_jobs.values()), {}
+            else:
+                full_jobs = [j for k, j in committed_jobs.items()
+                             if k in full_keys]
+                rest = {k: j for k, j in committed_jobs.items()
+                        if k not in full_keys}
+            changed, _ = host.load().set_podgroup_phase(full_jobs, running)
+            if store is not None and changed:
+                if rest:    # interleaved with the rest: publish in the loop
+                    flipped = {id(j) for j in changed}
+                    rest = committed_jobs
+                else:
+                    for job in changed:
+                        ssn.cache.update_podgroup(job)
+            committed_jobs = rest
         seen = set()
         for key, job in committed_jobs.items():
+            if flipped and id(job) in flipped:
+                ssn.cache.update_podgroup(job)
+                continue
             real = alias.get(key) if alias else None
             if real is not None:
                 if real in seen:

@@ -11,6 +11,7 @@ scheduling gate is lifted from a job's pods once its queue admits it.
 from __future__ import annotations
 
 from ...api.types import PodGroupPhase
+from ...ops import host
 
 QUEUE_GATE = "volcano.sh/queue-allocation-gate"
 
@@ -60,8 +61,10 @@ class EnqueueAction:
             self._admit_queue(ssn, q, None, rows=rows, jt=jt)
 
     def _admit_queue(self, ssn, q, jobs_q, rows=None, jt=None) -> None:
-        if jobs_q is None:
-            jobs_q = [jt.jobs[int(k)] for k in rows]
+        columnar = jobs_q is None
+        if columnar:
+            jjobs = jt.jobs
+            jobs_q = [jjobs[k] for k in rows.tolist()]
         elif ssn.job_enqueueable_fns and ssn.node_tensors is not None:
             # non-columnar path: same unrepresented-resource admission
             # veto the columnar path applies via jt.minres_bad
@@ -85,6 +88,24 @@ class EnqueueAction:
                     c()
                 inq = PodGroupPhase.INQUEUE.value
                 from ..jobtable import PH_INQUEUE
+                if columnar and host.native_jobs_enabled():
+                    # rows are the jobs' table rows: one native call for
+                    # the phase stores, one array store for the column
+                    _, gated = host.load().set_podgroup_phase(
+                        jobs_q, inq, True)
+                    jt.phase[rows] = PH_INQUEUE
+                    if store is not None and gated:
+                        for job in jobs_q:      # per-job call order kept
+                            ssn.cache.update_podgroup(job)
+                            if getattr(job, "_gated", 0):
+                                self._lift_queue_gates(ssn, job)
+                    elif store is not None:
+                        for job in jobs_q:
+                            ssn.cache.update_podgroup(job)
+                    else:
+                        for job in gated:
+                            self._lift_queue_gates(ssn, job)
+                    return
                 for job in jobs_q:
                     if job.podgroup is not None:
                         job.podgroup.status.phase = inq

@@ -28,6 +28,7 @@ from typing import Dict, List, Optional
 import numpy as np
 
 from ..api.types import PodGroupPhase, TaskStatus
+from ..ops import host
 
 # phase encoding
 PH_PENDING, PH_INQUEUE, PH_RUNNING, PH_OTHER = 0, 1, 2, 3
@@ -83,12 +84,20 @@ class JobTable:
         J = len(jobs_dict)
         rebuild = (epoch != self._epoch or J != len(self.jobs)
                    or nt.r != self._r)
+        native = host.native_jobs_enabled()
         if rebuild:
             self.jobs = list(jobs_dict.values())
             self._epoch = epoch
             self._r = nt.r
             self._build_static(nt)
             self._queue_index = None
+            if native:      # no row can be dirty right after a rebuild
+                self._scan_native()
+        elif native:
+            # one native pass: dynamic columns + the version scan
+            dirty = self._scan_native()
+            if dirty:
+                self._refresh_static_rows(dirty, nt)
         else:
             # per-job static refresh for bumped versions
             vers = self._vers
@@ -102,7 +111,21 @@ class JobTable:
             self.qi = np.fromiter(
                 (qidx.get(q, -1) for q in self._qnames),
                 dtype=np.int64, count=len(self._qnames))
-        self._refresh_dynamic()
+        if not native:
+            self._refresh_dynamic()
+
+    def _scan_native(self) -> List[int]:
+        """``_refresh_dynamic`` plus the ``_tver`` scan as one call into the
+        host extension; returns the dirty rows."""
+        J = len(self.jobs)
+        self.occ = np.empty(J, dtype=np.int64)
+        self.npend = np.empty(J, dtype=np.int64)
+        self.nfailed = np.empty(J, dtype=np.int64)
+        self.phase = np.empty(J, dtype=np.int8)
+        return host.load().scan_jobs(
+            self.jobs, TaskStatus.PENDING, TaskStatus.FAILED, _PHASE_MAP,
+            PH_PENDING, PH_OTHER, self._vers, self.occ, self.npend,
+            self.nfailed, self.phase)
 
     def _build_static(self, nt) -> None:
         jobs = self.jobs
