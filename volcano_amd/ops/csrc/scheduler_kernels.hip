@@ -77,8 +77,11 @@ DEVINL NodeScore node_score_one(
         float e = extra ? extra[off] : 0.f;
         float avail = a - u + e;
         float rq = req[r];
+        // the fit test covers EVERY dim, as in the oracle: a node over-
+        // committed (used > alloc) in a dim the class does not request
+        // is still not a place to put more work
+        feasible = feasible && (avail + EPS >= rq);
         if (rq > EPS) {
-            feasible = feasible && (avail + EPS >= rq);
             float cc = (avail + EPS) / rq;     // clamp before the int
             if (cc > (float)BIG_CAP) cc = (float)BIG_CAP;  // cast: UB on inf
             long long c = (long long)floorf(cc);
@@ -220,6 +223,7 @@ __device__ void dev_select_commit(
     __shared__ int s_remaining;
     __shared__ int s_cursor;
     __shared__ int s_take;
+    __shared__ int s_go;
     __shared__ long long s_budget;
 
     const int tid = threadIdx.x;
@@ -262,15 +266,24 @@ __device__ void dev_select_commit(
             ValIdx b; b.v = NEG_INF; b.i = INT32_MAX;
             if (lane < SC_WAVES) b = s_wave[lane];
             b = wave_reduce(b);
-            if (lane == 0) s_best = b;
+            // lane 0 of wave 0 IS thread 0, the only writer of
+            // s_remaining/s_cursor: it decides "continue" here and
+            // publishes it with the winner.  Other threads must not read
+            // the two counters themselves — thread 0 updates them below
+            // with no barrier in between, so a late wave could see the
+            // post-update values and leave one iteration early.
+            if (lane == 0) {
+                s_best = b;
+                s_go = (b.v != NEG_INF && s_remaining > 0 && s_cursor < K)
+                    ? 1 : 0;
+            }
         }
         __syncthreads();
 
         ValIdx best = s_best;
-        if (best.v == NEG_INF || s_remaining <= 0 || s_cursor >= K) break;
+        if (!s_go) break;
 
-        // take is published through LDS: every thread reading s_remaining
-        // directly would race with thread 0's decrement below
+        // take is published through LDS for the same reason
         if (tid == 0) {
             s_take = min(cap[best.i], s_remaining);
             log_nodes[s_cursor] = best.i;
@@ -463,6 +476,9 @@ __global__ void cond_revert_kernel(
 // monotonic float->uint map, then invert so ASCENDING key == score DESC
 DEVINL unsigned score_key(float s) {
     unsigned u = __float_as_uint(s);
+    // -0.0 == +0.0 for the oracle's stable sort and the serial argmax:
+    // both zeros share one key so the index alone orders them
+    if (u == 0x80000000u) u = 0u;
     unsigned m = (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;
     return ~(u ^ m);
 }
@@ -888,7 +904,7 @@ topk_kernel(
 
 // 256 threads / 4 waves: enough waves to hide the L2 latency of the
 // touched-list re-scoring (one wave measured 5x slower — latency
-// bound), small enough that the two per-pop barriers stay cheap.
+// bound), small enough that the three per-pop barriers stay cheap.
 // Scalar decisions (budget/cap/take) are computed REDUNDANTLY by every
 // thread from the same memory — uniform by construction, no broadcast
 // barrier needed; the cross-wave argmax merge is one LDS write + one
@@ -1038,6 +1054,9 @@ select_chain_kernel(
             // live capacity of the chosen node: per-dim candidates on
             // lanes < R, wave min-reduce (uniform across waves; untouched
             // nodes keep their snapshot capacity by definition)
+            // touched[] is read here, with the capacity loads: wave 0
+            // stores to both below
+            const bool was_touched = touched[best.i] != 0;
             long long ccand = BIG_CAP;
             if (lane < R) {
                 float rq = req[lane];
@@ -1056,6 +1075,10 @@ select_chain_kernel(
                                                           off));
             const long long cap = __shfl((long long)ccand, 0);
             int take = (int)min(cap, (long long)remaining);
+            // every wave has read used[]/touched[] of the winner before
+            // any of them is stored to — otherwise a late wave computes
+            // a different take / tcount and the mirrors diverge
+            __syncthreads();
             if (take > 0) {
                 if (tid == 0) {
                     ln[cursor] = best.i;
@@ -1066,7 +1089,7 @@ select_chain_kernel(
                 if (tid < R)
                     used[(size_t)tid * N + best.i] += (float)take * req[tid];
             }
-            if (!touched[best.i]) {
+            if (!was_touched) {
                 // mark even on take==0 (defensive: a zero-cap winner must
                 // never win again; cannot occur when snapshot caps hold)
                 if (tid == 0) {

@@ -54,6 +54,8 @@ def _load():
     lib.vamd_finalize_job.restype = None
     lib.vamd_cond_revert.restype = None
     lib.vamd_run_cycle.restype = None
+    lib.vamd_fused_score_select.restype = None
+    lib.vamd_topk.restype = None
     _lib = lib
     return lib
 
@@ -123,6 +125,37 @@ def cond_revert(flag, log_nodes, log_counts, log_len, req, used_t,
         _p(flag), _p(log_nodes), _p(log_counts), _p(log_len), _p(req),
         _p(used_t), _p(queue_alloc_row), _p(placed), _p(job_placed),
         c_int(N), c_int(R), _stream())
+
+
+def fused_score_select(alloc_t, used_t, extra_t, ready, taints, planes_t,
+                       req, tolerated, require, forbid, w_least, w_most,
+                       w_bal, dim_w, bias, score, cap, ntasks,
+                       queue_alloc_row, queue_limit_row, log_nodes,
+                       log_counts, log_len, placed, job_placed, fuse_min):
+    """score_cap + serial select_commit in one launch (the N <= 4096
+    small-class path of the cycle runner)."""
+    lib = _load()
+    R, N = alloc_t.shape
+    W = planes_t.shape[0]
+    K = log_nodes.shape[0]
+    lib.vamd_fused_score_select(
+        _p(alloc_t), _p(used_t), _p(extra_t), _p(ready), _p(taints),
+        _p(planes_t), _p(req), c_int64(int(tolerated)), _p(require),
+        _p(forbid), c_float(w_least), c_float(w_most), c_float(w_bal),
+        _p(dim_w), _p(bias), _p(score), _p(cap), c_int(int(ntasks)),
+        _p(queue_alloc_row), _p(queue_limit_row), _p(log_nodes),
+        _p(log_counts), _p(log_len), _p(placed), _p(job_placed),
+        c_int(int(fuse_min)), c_int(N), c_int(R), c_int(W), c_int(K),
+        _stream())
+
+
+def topk(score_buf, count, topk_vals, topk_ids):
+    """Top-16 candidates of the first ``count`` rows of score_buf [*, N];
+    chosen entries are knocked out of the row."""
+    lib = _load()
+    N = score_buf.shape[1]
+    lib.vamd_topk(_p(score_buf), c_int(int(count)), _p(topk_vals),
+                  _p(topk_ids), c_int(N), _stream())
 
 
 # -- whole-cycle runner ------------------------------------------------------
