@@ -1,0 +1,292 @@
+"""Inputs and an independent model for the topology-spread select.
+
+``model`` is the per-instance definition of the spread fill in plain Python
+(no torch, no shared code with ``reference.spread_select_commit``).  Scores
+are a few multiples of 0.25 (exact in f32, large tie groups), requests and
+usage small integers, so every f32 operation is exact and "equal" means
+bit-equal.  Plain module: no fixtures, no collection hooks.
+"""
+
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import List, Optional
+
+import numpy as np
+import torch
+
+from volcano_amd.ops import reference as ref
+
+NEG_INF = float("-inf")
+BIG = 1.0e18
+
+
+@dataclass
+class SpreadCase:
+    name: str
+    score: np.ndarray        # [N] f32 (-inf = infeasible)
+    cap: np.ndarray          # [N] i32
+    req: np.ndarray          # [R] f32
+    ntasks: int
+    used: np.ndarray         # [N, R] f32
+    queue_alloc: np.ndarray  # [R] f32
+    queue_limit: np.ndarray  # [R] f32
+    dom_of: np.ndarray       # [N] i32
+    dom_count: np.ndarray    # [D] i32
+    max_skew: int
+    fuse_min: int = -1       # >= 0: single-class gang minimum (kernel side)
+
+    @property
+    def N(self):
+        return len(self.score)
+
+    @property
+    def D(self):
+        return len(self.dom_count)
+
+    @property
+    def K(self):
+        return max(1, min(self.ntasks, self.N))
+
+
+def quota_of(case: SpreadCase) -> int:
+    """Instances the queue still admits (integer inputs: exact)."""
+    q = 2 ** 30
+    for r in range(len(case.req)):
+        if case.req[r] > 0:
+            head = float(case.queue_limit[r]) - float(case.queue_alloc[r])
+            q = min(q, max(0, int(np.floor(head / float(case.req[r])))))
+    return q
+
+
+def model(score, cap, dom_of, count, skew, budget):
+    """Independent per-instance model -> (placement sequence, counts,
+    per-step record of (node, blocked-by-skew nodes existed, tie size))."""
+    count = list(count)
+    rem = [c if s > NEG_INF and d >= 0 else 0
+           for s, c, d in zip(score, cap, dom_of)]
+    seq, steps = [], []
+    while len(seq) < budget:
+        low = min(count)
+        live = [n for n in range(len(rem)) if rem[n] > 0]
+        ok = [n for n in live if count[dom_of[n]] + 1 - low <= skew]
+        if not ok:
+            steps.append((None, bool(live), 0))
+            break
+        top = max(score[n] for n in ok)
+        tie = [n for n in ok if score[n] == top]
+        n = tie[0]
+        rem[n] -= 1
+        count[dom_of[n]] += 1
+        seq.append(n)
+        steps.append((n, len(ok) < len(live), len(tie)))
+    return seq, count, steps
+
+
+def model_of(case: SpreadCase):
+    return model(case.score.tolist(), case.cap.tolist(),
+                 case.dom_of.tolist(), case.dom_count.tolist(),
+                 case.max_skew, min(case.ntasks, quota_of(case)))
+
+
+def log_of(seq: List[int]):
+    """(nodes, counts): one entry per node in order of first placement."""
+    nodes, counts = [], {}
+    for n in seq:
+        if n not in counts:
+            nodes.append(n)
+            counts[n] = 0
+        counts[n] += 1
+    return nodes, [counts[n] for n in nodes]
+
+
+def random_case(name, N, D, skew, R, seed, *, ntasks=None, quota=None,
+                unlabeled=0.1, infeasible=0.15, dead_domain=False,
+                unbalanced=False, cap_hi=4, fuse_min=-1) -> SpreadCase:
+    rng = np.random.RandomState(seed)
+    D = min(D, N)
+    # every domain owns at least one node when N allows it
+    dom_of = np.concatenate([np.arange(D), rng.randint(0, D, size=N - D)])
+    dom_of = dom_of[rng.permutation(N)].astype(np.int32)
+    if N > 1:
+        dom_of[rng.rand(N) < unlabeled] = -1
+    score = (rng.randint(0, 4, size=N) * 0.25).astype(np.float32)
+    score[rng.rand(N) < infeasible] = NEG_INF
+    cap = rng.randint(0, cap_hi + 1, size=N).astype(np.int32)
+    if dead_domain and D > 1:
+        score[dom_of == D - 1] = NEG_INF
+    count = rng.randint(0, 2, size=D).astype(np.int32)
+    if unbalanced:
+        count[0] += 3 + skew
+        if D > 2:
+            count[1] += 1 + skew
+    req = np.zeros(R, dtype=np.float32)
+    req[0] = 1.0
+    for r in range(1, min(R, 4)):
+        req[r] = float(rng.randint(0, 3))
+    used = rng.randint(0, 8, size=(N, R)).astype(np.float32)
+    qa = rng.randint(0, 5, size=R).astype(np.float32)
+    ql = np.full(R, BIG, dtype=np.float32)
+    room = int(cap[(score > NEG_INF) & (dom_of >= 0)].sum())
+    if ntasks is None:
+        ntasks = max(1, min(room // 2 + 1, 96))
+    if quota is not None:
+        ql[0] = qa[0] + float(quota)
+    return SpreadCase(name, score, cap, req, int(ntasks), used, qa, ql,
+                      dom_of, count, skew, fuse_min)
+
+
+# --------------------------------------------------------------------------
+# plan-level case: spread classes among plain, bulk and reverting ones
+# --------------------------------------------------------------------------
+
+@dataclass
+class SpreadPlanCase:
+    base: object                   # _kernel_cases.PlanCase
+    spread: dict                   # class index -> (group, max_skew)
+    groups: list                   # [(dom_of i32 [N], count i32 [D])]
+    roles: dict                    # name -> class index
+
+
+def spread_plan_case(N=1000, R=5, W=1, seed=21, bulk=True) -> SpreadPlanCase:
+    """Job order: [one 600-task plain class] · a two-role gang whose first
+    role spreads over group 0 and whose second role misses its minimum
+    (the job reverts) · 36 small plain single-class jobs (a chain run) · a
+    spread job of group 0 (must see the restored counts) · a spread job
+    over group 1 (one domain per node) that cannot reach its gang minimum
+    and reverts in the select · a spread job of group 1 · 8 plain jobs."""
+    import _kernel_cases as kc
+    rng = np.random.RandomState(seed)
+    st = kc.dyadic_state(N, R, W, seed)
+    classes, jobs, spread, roles = [], [], {}, {}
+
+    def add_job(cls, occupied, min_avail):
+        b = len(classes)
+        classes.extend(cls)
+        jobs.append((b, len(classes), occupied, min_avail))
+
+    def small_jobs(count):
+        for j in range(count):
+            n = int(rng.randint(1, 13))
+            need = n + 1 if j % 11 == 3 else max(1, n - 1)
+            add_job([kc._class(rng, R, W, n, 2 if j % 5 == 4 else j % 2,
+                               bias_row=j % 2 if j % 3 == 0 else None,
+                               plain=True)], 0, need)
+
+    if bulk:
+        roles["bulk"] = len(classes)
+        add_job([kc._class(rng, R, W, 600, 0, plain=True)], 0, 300)
+    roles["gang_spread"] = len(classes)
+    spread[len(classes)] = (0, 1)
+    add_job([kc._class(rng, R, W, 9, 0, min_needed=1, plain=True),
+             kc._class(rng, R, W, 3, 1, min_needed=4, plain=True)], 0, 5)
+    small_jobs(36)
+    roles["spread"] = len(classes)
+    spread[len(classes)] = (0, 2)
+    add_job([kc._class(rng, R, W, 14, 0, plain=True)], 0, 3)
+    roles["host_revert"] = len(classes)
+    spread[len(classes)] = (1, 1)
+    add_job([kc._class(rng, R, W, 5, 1, plain=True)], 0, N + 1)
+    roles["host"] = len(classes)
+    spread[len(classes)] = (1, 1)
+    # with the bulk class in the plan this one is bulk-sized too: a spread
+    # class must not take the sort-based select whatever its size
+    add_job([kc._class(rng, R, W, 600 if bulk else 40, 1, plain=True)],
+            0, 10)
+    small_jobs(8)
+
+    dom0 = rng.randint(0, 3, size=N).astype(np.int32)
+    dom0[rng.rand(N) < 0.1] = -1
+    groups = [(dom0, np.array([2, 0, 1], dtype=np.int32)),
+              (np.arange(N, dtype=np.int32),
+               (rng.rand(N) < 0.3).astype(np.int32))]
+    ql, qa = kc._queues(rng, R, limit_dim0=30)
+    base = kc.PlanCase("spread", N, R, W, st, classes, jobs, ql, qa,
+                       kc._bias_rows(rng, N, 2))
+    return SpreadPlanCase(base, spread, groups, roles)
+
+
+def build_spread_plan(case: SpreadPlanCase, device):
+    import _kernel_cases as kc
+    plan = kc.build_plan(case.base, device)
+    for dom_of, count in case.groups:
+        plan.add_spread_group(dom_of.copy(), count.copy())
+    for c, sp in case.spread.items():
+        plan.classes[c].spread = sp
+    return plan
+
+
+def spread_snapshot(plan, res) -> dict:
+    import _kernel_cases as kc
+    snap = kc.snapshot(plan, res)
+    snap["spread_counts"] = [t.cpu().numpy().copy()
+                             for t in plan.spread_counts]
+    return snap
+
+
+def compare_spread(want: dict, got: dict) -> None:
+    import _kernel_cases as kc
+    kc.compare_results(want, got)
+    for g, (a, b) in enumerate(zip(want["spread_counts"],
+                                   got["spread_counts"])):
+        assert np.array_equal(a, b), f"group {g}: final dom_count differs"
+
+
+def run_plan_oracle(case: SpreadPlanCase):
+    """run_plan_torch on the CPU -> (snapshot, records of every oracle
+    spread select: its inputs and the model's step flags)."""
+    from volcano_amd.scheduler import plan as planmod
+    plan = build_spread_plan(case, "cpu")
+    records = []
+    real = ref.spread_select_commit
+
+    def spy(score, cap, req, ntasks, used, qa, ql, ln, lc, ll, placed, jp,
+            dom_of, dom_count, max_skew):
+        rec = dict(score=score.tolist(), cap=cap.tolist(),
+                   dom_of=dom_of.tolist(), count=dom_count.tolist(),
+                   skew=max_skew, ntasks=int(ntasks))
+        real(score, cap, req, ntasks, used, qa, ql, ln, lc, ll, placed, jp,
+             dom_of, dom_count, max_skew)
+        rec["placed"] = int(placed)
+        rec["steps"] = model(rec["score"], rec["cap"], rec["dom_of"],
+                             rec["count"], max_skew, rec["placed"] + 1)[2]
+        records.append(rec)
+
+    planmod.ref.spread_select_commit = spy
+    try:
+        res = planmod.run_plan_torch(plan)
+    finally:
+        planmod.ref.spread_select_commit = real
+    return spread_snapshot(plan, res), records
+
+
+def run_oracle(case: SpreadCase, *, revert: Optional[bool] = None):
+    """reference.spread_select_commit on fresh copies.  ``revert``: apply
+    spread_revert afterwards (None: decide from case.fuse_min, as the
+    kernel does in place)."""
+    t = torch.from_numpy
+    used = t(case.used.copy())
+    qa = t(case.queue_alloc.copy())
+    cnt = t(case.dom_count.copy())
+    dom = t(case.dom_of.copy())
+    req = t(case.req.copy())
+    ln = torch.zeros(case.K, dtype=torch.int32)
+    lc = torch.zeros(case.K, dtype=torch.int32)
+    ll = torch.zeros((), dtype=torch.int32)
+    placed = torch.zeros((), dtype=torch.int32)
+    jp = torch.full((), 7, dtype=torch.int32)
+    ref.spread_select_commit(
+        t(case.score.copy()), t(case.cap.copy()), req, case.ntasks, used,
+        qa, t(case.queue_limit.copy()), ln, lc, ll, placed, jp, dom, cnt,
+        case.max_skew)
+    before = dict(log_nodes=ln.numpy().copy(), log_counts=lc.numpy().copy(),
+                  placed=int(placed))
+    if revert is None:
+        revert = case.fuse_min >= 0 and int(placed) < case.fuse_min
+    if revert:
+        ref.spread_revert(torch.zeros((), dtype=torch.uint8), ln, lc, ll,
+                          req, used, qa, placed, jp, dom, cnt)
+    return dict(log_nodes=ln.numpy(), log_counts=lc.numpy(),
+                log_len=int(ll), placed=int(placed), job_placed=int(jp),
+                used=used.numpy(), queue_alloc=qa.numpy(),
+                dom_count=cnt.numpy(), reverted=bool(revert), before=before)

@@ -28,7 +28,19 @@ static bool megacycle_enabled() {
     return e != nullptr && atoi(e) != 0;
 }
 
-extern "C" void vamd_run_cycle(
+// Spread classes of a plan (host-side view; all null when the plan has
+// none, and then nothing below changes a single launch).
+struct SpreadArgs {
+    const int32_t* group = nullptr;      // [C] group index or -1
+    const int32_t* skew = nullptr;       // [C]
+    const int32_t* dom_of = nullptr;     // device [G, N]
+    int32_t* count = nullptr;            // device, flat
+    const int32_t* count_off = nullptr;  // [G]
+    const int32_t* domains = nullptr;    // [G]
+    void* scratch = nullptr;             // device
+};
+
+static void run_cycle_impl(
     const VamdClassDesc* classes, int n_classes,
     const VamdJobDesc* jobs, int n_jobs,
     const float* alloc, float* used, const float* extra,
@@ -43,12 +55,19 @@ extern "C" void vamd_run_cycle(
     int* log_nodes, int* log_counts, int* log_len,
     int* class_placed, int* job_placed, uint8_t* job_flag,
     unsigned* sort_scratch,
-    int N, int R, int W, hipStream_t stream)
+    int N, int R, int W, const SpreadArgs& sp, hipStream_t stream)
 {
+    auto spread_of = [&](int c) {
+        return sp.group != nullptr ? sp.group[c] : -1;
+    };
     bool any_bulk = false;
-    for (int c = 0; c < n_classes; ++c)
-        if (classes[c].ntasks >= 512) { any_bulk = true; break; }
-    if (megacycle_enabled() && !any_bulk && n_classes >= 32) {
+    bool any_spread = false;
+    for (int c = 0; c < n_classes; ++c) {
+        if (classes[c].ntasks >= 512) any_bulk = true;
+        if (spread_of(c) >= 0) any_spread = true;
+    }
+    // the megacycle kernel has no spread select: such a plan runs per class
+    if (megacycle_enabled() && !any_bulk && !any_spread && n_classes >= 32) {
         // stage descriptors + taint masks on device (stream-ordered)
         size_t sz_c = (size_t)n_classes * sizeof(VamdClassDesc);
         size_t sz_j = (size_t)n_jobs * sizeof(VamdJobDesc);
@@ -92,6 +111,7 @@ extern "C" void vamd_run_cycle(
     auto chainable = [&](int j) {
         const VamdJobDesc& jb = jobs[j];
         if (jb.class_end - jb.class_begin != 1) return false;
+        if (spread_of(jb.class_begin) >= 0) return false;  // breaks a chunk
         return classes[jb.class_begin].ntasks < 512;
     };
     bool chain_on = false;
@@ -223,6 +243,30 @@ extern "C" void vamd_run_cycle(
                 fuse_min = need > 0 ? need : 0;
             }
 
+            const int g = spread_of(c);
+            if (g >= 0) {
+                // topology spread: eligibility moves with every single
+                // placement — always score + spread select, whatever the
+                // class size
+                vamd_score_cap(alloc, used, ext, ready, taints, planes,
+                               class_req + (size_t)c * R, class_tol[c],
+                               class_require + (size_t)c * W,
+                               class_forbid + (size_t)c * W,
+                               cd.w_least, cd.w_most, cd.w_bal, dim_w, b,
+                               score_scratch, cap_scratch, N, R, W, stream);
+                vamd_spread_select(
+                    score_scratch, cap_scratch, class_req + (size_t)c * R,
+                    cd.ntasks, used,
+                    queue_alloc + (size_t)cd.queue_idx * R,
+                    queue_limit + (size_t)cd.queue_idx * R,
+                    log_nodes + cd.log_off, log_counts + cd.log_off,
+                    log_len + c, class_placed + c, job_placed + j,
+                    sp.dom_of + (size_t)g * N, sp.count + sp.count_off[g],
+                    sp.domains[g], sp.skew[c], fuse_min, sp.scratch,
+                    N, R, cd.log_cap, stream);
+                continue;
+            }
+
             if (cd.ntasks < 512 && N <= 4096) {
                 // small class on a small inventory: ONE fused launch
                 // (score in-block + select).  At larger N the one-block
@@ -268,6 +312,19 @@ extern "C" void vamd_run_cycle(
                               stream);
             for (int c = job.class_begin; c < job.class_end; ++c) {
                 const VamdClassDesc& cd = classes[c];
+                const int g = spread_of(c);
+                if (g >= 0) {
+                    vamd_spread_revert(
+                        job_flag + j, log_nodes + cd.log_off,
+                        log_counts + cd.log_off, log_len + c,
+                        class_req + (size_t)c * R, used,
+                        queue_alloc + (size_t)cd.queue_idx * R,
+                        class_placed + c, job_placed + j,
+                        sp.dom_of + (size_t)g * N,
+                        sp.count + sp.count_off[g], sp.domains[g], N, R,
+                        stream);
+                    continue;
+                }
                 vamd_cond_revert(job_flag + j, log_nodes + cd.log_off,
                                  log_counts + cd.log_off, log_len + c,
                                  class_req + (size_t)c * R, used,
@@ -280,4 +337,69 @@ extern "C" void vamd_run_cycle(
     }
     if (chain_blob != nullptr)
         (void)hipFreeAsync(chain_blob, stream);
+}
+
+extern "C" void vamd_run_cycle(
+    const VamdClassDesc* classes, int n_classes,
+    const VamdJobDesc* jobs, int n_jobs,
+    const float* alloc, float* used, const float* extra,
+    const uint8_t* ready, const int64_t* taints, const int64_t* planes,
+    const float* bias,
+    const float* bias_rows,
+    const float* class_req, const int64_t* class_tol,
+    const int64_t* class_require, const int64_t* class_forbid,
+    const int32_t* class_min, const float* dim_w,
+    float* queue_alloc, const float* queue_limit,
+    float* score_scratch, int* cap_scratch,
+    int* log_nodes, int* log_counts, int* log_len,
+    int* class_placed, int* job_placed, uint8_t* job_flag,
+    unsigned* sort_scratch,
+    int N, int R, int W, hipStream_t stream)
+{
+    run_cycle_impl(classes, n_classes, jobs, n_jobs, alloc, used, extra,
+                   ready, taints, planes, bias, bias_rows, class_req,
+                   class_tol, class_require, class_forbid, class_min, dim_w,
+                   queue_alloc, queue_limit, score_scratch, cap_scratch,
+                   log_nodes, log_counts, log_len, class_placed, job_placed,
+                   job_flag, sort_scratch, N, R, W, SpreadArgs(), stream);
+}
+
+extern "C" void vamd_run_cycle_spread(
+    const VamdClassDesc* classes, int n_classes,
+    const VamdJobDesc* jobs, int n_jobs,
+    const float* alloc, float* used, const float* extra,
+    const uint8_t* ready, const int64_t* taints, const int64_t* planes,
+    const float* bias,
+    const float* bias_rows,
+    const float* class_req, const int64_t* class_tol,
+    const int64_t* class_require, const int64_t* class_forbid,
+    const int32_t* class_min, const float* dim_w,
+    float* queue_alloc, const float* queue_limit,
+    float* score_scratch, int* cap_scratch,
+    int* log_nodes, int* log_counts, int* log_len,
+    int* class_placed, int* job_placed, uint8_t* job_flag,
+    unsigned* sort_scratch,
+    int N, int R, int W,
+    const int32_t* class_spread_group, const int32_t* class_spread_skew,
+    const int32_t* spread_dom_of, int32_t* spread_count,
+    const int32_t* spread_count_off, const int32_t* spread_domains,
+    void* spread_scratch, hipStream_t stream)
+{
+    SpreadArgs sp;
+    if (class_spread_group != nullptr && spread_dom_of != nullptr &&
+            spread_count != nullptr && spread_scratch != nullptr) {
+        sp.group = class_spread_group;
+        sp.skew = class_spread_skew;
+        sp.dom_of = spread_dom_of;
+        sp.count = spread_count;
+        sp.count_off = spread_count_off;
+        sp.domains = spread_domains;
+        sp.scratch = spread_scratch;
+    }
+    run_cycle_impl(classes, n_classes, jobs, n_jobs, alloc, used, extra,
+                   ready, taints, planes, bias, bias_rows, class_req,
+                   class_tol, class_require, class_forbid, class_min, dim_w,
+                   queue_alloc, queue_limit, score_scratch, cap_scratch,
+                   log_nodes, log_counts, log_len, class_placed, job_placed,
+                   job_flag, sort_scratch, N, R, W, sp, stream);
 }

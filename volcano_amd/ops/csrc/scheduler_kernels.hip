@@ -701,6 +701,283 @@ bulk_select_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// K2 select under a topology-spread constraint (maxSkew, DoNotSchedule),
+// enforced before EVERY placement — oracle: reference.py
+// spread_select_commit.  Scores are static within the class, but a node
+// is eligible only while count[its domain] + 1 - min(count) <= max_skew,
+// and every placement moves a count, so the fill is a true per-instance
+// loop (bounded by the budget):
+//
+//   * head[d] caches the best remaining node of domain d as one 64-bit
+//     key (ordered score << 32 | ~index): the larger key is the better
+//     score, ties the lower index.  0 = domain has no node left.
+//   * one iteration = one pass over the D domains (count + head per
+//     domain, O(D/1024) per thread) feeding ONE block reduce that yields
+//     the best eligible head and n0 = #domains sitting at the minimum m.
+//     Thread 0 places one instance and advances m when the placement
+//     took the last domain off the minimum (n0 == 1) — no second reduce.
+//   * a head is rescanned (O(N/1024) per thread) only when its node's
+//     remaining capacity reaches 0.
+//
+// Barrier conventions of dev_select_commit: thread 0 owns every counter
+// and publishes go/rescan together; loop exits are read block-uniformly
+// after a barrier; no barrier under divergent control flow.
+// `score` and `cap` are consumed (cap counts down, used-up nodes -> -inf);
+// `used` takes ONE (float)count * req per log entry after the loop, which
+// is what keeps it bit-equal to the oracle.
+// ---------------------------------------------------------------------------
+#define SP_THREADS 1024
+#define SP_WAVES (SP_THREADS / WAVE)
+
+DEVINL unsigned long long spread_key(float s, int i) {
+    unsigned u = __float_as_uint(s);
+    if (u == 0x80000000u) u = 0u;              // -0.0 ties with +0.0
+    u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;  // ascending in the score
+    return ((unsigned long long)u << 32) | (0xFFFFFFFFu - (unsigned)i);
+}
+
+DEVINL int spread_key_node(unsigned long long k) {
+    return (int)(0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull));
+}
+
+DEVINL unsigned long long head_load(unsigned long long* h) {
+    return __hip_atomic_load(h, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// keys only grow between two resets, so a stale read can only let a
+// redundant atomic through, never drop a better key
+DEVINL void head_offer(unsigned long long* h, unsigned long long k) {
+    if (k > head_load(h))
+        __hip_atomic_fetch_max(h, k, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+DEVINL unsigned long long wave_max_u64(unsigned long long x) {
+    for (int off = WAVE / 2; off > 0; off >>= 1) {
+        unsigned long long o = __shfl_down(x, off);
+        x = o > x ? o : x;
+    }
+    return x;
+}
+
+__global__ void __launch_bounds__(SP_THREADS)
+spread_select_kernel(
+    float* __restrict__ score,        // [N] consumed
+    int* __restrict__ cap,            // [N] consumed (remaining capacity)
+    const float* __restrict__ req,    // [R]
+    int ntasks,
+    float* __restrict__ used,         // [R, N] in place
+    float* __restrict__ queue_alloc,  // [R] in place
+    const float* __restrict__ queue_limit, // [R]
+    int* __restrict__ log_nodes,      // [K]
+    int* __restrict__ log_counts,     // [K]
+    int* __restrict__ log_len,        // [1]
+    int* __restrict__ placed,         // [1]
+    int* __restrict__ job_placed,     // [1]
+    const int* __restrict__ dom_of,   // [N] domain id, -1 = unlabeled
+    int* __restrict__ dom_count,      // [D] in place
+    int D, int max_skew, int fuse_min,
+    unsigned long long* __restrict__ head,  // [D] scratch
+    int* __restrict__ slot,           // [N] scratch: node -> log entry
+    int N, int R, int K)
+{
+    __shared__ unsigned long long s_wkey[SP_WAVES];
+    __shared__ int s_wint[SP_WAVES];
+    __shared__ int s_budget;
+    __shared__ int s_m;         // min(dom_count) for the coming iteration
+    __shared__ int s_cursor;
+    __shared__ int s_total;
+    __shared__ int s_go;
+    __shared__ int s_rescan;    // domain whose head must be rebuilt, or -1
+
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wid = tid / WAVE;
+
+    if (tid == 0) {
+        long long quota = BIG_CAP;
+        for (int r = 0; r < R; ++r) {
+            float rq = req[r];
+            if (rq > EPS) {
+                float hd = queue_limit[r] - queue_alloc[r];
+                float qq = (hd + EPS) / rq;
+                if (qq > (float)BIG_CAP) qq = (float)BIG_CAP;
+                long long q = (long long)floorf(qq);
+                quota = min(quota, max(q, 0ll));
+            }
+        }
+        long long b = min((long long)ntasks, quota);
+        s_budget = (D > 0 && b > 0) ? (int)b : 0;
+        s_cursor = 0;
+        s_total = 0;
+    }
+    for (int d = tid; d < D; d += SP_THREADS) head[d] = 0ull;
+    __syncthreads();
+
+    // nodes that can never take an instance leave the score vector; the
+    // others offer themselves as their domain's head
+    for (int i = tid; i < N; i += SP_THREADS) {
+        slot[i] = -1;
+        float s = score[i];
+        int d = dom_of[i];
+        if (s > NEG_INF && d >= 0 && d < D && cap[i] > 0)
+            head_offer(head + d, spread_key(s, i));
+        else
+            score[i] = NEG_INF;
+    }
+    {
+        int lmin = INT32_MAX;
+        for (int d = tid; d < D; d += SP_THREADS)
+            lmin = min(lmin, dom_count[d]);
+        for (int off = WAVE / 2; off > 0; off >>= 1)
+            lmin = min(lmin, __shfl_down(lmin, off));
+        if (lane == 0) s_wint[wid] = lmin;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int m = INT32_MAX;
+        for (int w = 0; w < SP_WAVES; ++w) m = min(m, s_wint[w]);
+        s_m = m;
+    }
+    __syncthreads();
+
+    const int budget = s_budget;
+    for (int it = 0; it < budget; ++it) {
+        const int m = s_m;
+        unsigned long long loc = 0ull;
+        int n0 = 0;
+        for (int d = tid; d < D; d += SP_THREADS) {
+            int c = dom_count[d];
+            unsigned long long k = head_load(head + d);
+            n0 += (c == m) ? 1 : 0;
+            if (c + 1 - m <= max_skew && k > loc) loc = k;
+        }
+        loc = wave_max_u64(loc);
+        for (int off = WAVE / 2; off > 0; off >>= 1)
+            n0 += __shfl_down(n0, off);
+        if (lane == 0) { s_wkey[wid] = loc; s_wint[wid] = n0; }
+        __syncthreads();
+        if (wid == 0) {
+            // 16 per-wave partials on lanes 0..15: four steps reach lane 0
+            unsigned long long k = lane < SP_WAVES ? s_wkey[lane] : 0ull;
+            int nm = lane < SP_WAVES ? s_wint[lane] : 0;
+            for (int off = SP_WAVES / 2; off > 0; off >>= 1) {
+                unsigned long long o = __shfl_down(k, off);
+                k = o > k ? o : k;
+                nm += __shfl_down(nm, off);
+            }
+            // lane 0 of wave 0 is thread 0, the only writer of the
+            // counters, the log, dom_count, cap and the head resets
+            if (lane == 0) {
+                int go = 0, rescan = -1;
+                if (k != 0ull) {
+                    const int node = spread_key_node(k);
+                    int sl = slot[node];
+                    if (sl >= 0 || s_cursor < K) {
+                        go = 1;
+                        const int d = dom_of[node];
+                        const int c = dom_count[d];
+                        dom_count[d] = c + 1;
+                        // the last domain at the minimum moved up
+                        if (c == m && nm == 1) s_m = m + 1;
+                        if (sl < 0) {
+                            sl = s_cursor;
+                            s_cursor = sl + 1;
+                            slot[node] = sl;
+                            log_nodes[sl] = node;
+                            log_counts[sl] = 1;
+                        } else {
+                            log_counts[sl] += 1;
+                        }
+                        const int left = cap[node] - 1;
+                        cap[node] = left;
+                        if (left <= 0) {
+                            score[node] = NEG_INF;
+                            __hip_atomic_store(head + d, 0ull,
+                                               __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_WORKGROUP);
+                            rescan = d;
+                        }
+                        s_total += 1;
+                    }
+                }
+                s_go = go;
+                s_rescan = rescan;
+            }
+        }
+        __syncthreads();
+        if (!s_go) break;            // block-uniform
+        const int rd = s_rescan;     // block-uniform
+        if (rd >= 0) {
+            unsigned long long best = 0ull;
+            for (int i = tid; i < N; i += SP_THREADS) {
+                if (dom_of[i] == rd) {
+                    float s = score[i];
+                    if (s > NEG_INF) {
+                        unsigned long long k = spread_key(s, i);
+                        if (k > best) best = k;
+                    }
+                }
+            }
+            best = wave_max_u64(best);
+            if (lane == 0 && best != 0ull) head_offer(head + rd, best);
+            __syncthreads();
+        }
+    }
+
+    __syncthreads();
+    const int total = s_total;
+    const int cursor = s_cursor;
+    const bool revert = (fuse_min >= 0) && (total < fuse_min);
+
+    if (revert) {
+        // single-class gang failed: nothing was applied to `used` yet;
+        // give the placements back to the group's domain counts
+        for (int e = tid; e < cursor; e += SP_THREADS) {
+            atomicSub(dom_count + dom_of[log_nodes[e]], log_counts[e]);
+            log_counts[e] = 0;
+        }
+        if (tid == 0) { *log_len = cursor; *placed = 0; }
+    } else {
+        for (int e = wid; e < cursor; e += SP_WAVES) {
+            int node = log_nodes[e];
+            int cnt = log_counts[e];
+            if (lane < R)
+                used[(size_t)lane * N + node] += (float)cnt * req[lane];
+        }
+        if (tid < R) queue_alloc[tid] += (float)total * req[tid];
+        if (tid == 0) {
+            *log_len = cursor;
+            *placed = total;
+            *job_placed += total;
+        }
+    }
+}
+
+// cond_revert for a spread class: the same rollback, plus the logged
+// placements leave the group's per-domain counts (integer atomics)
+__global__ void spread_revert_kernel(
+    const uint8_t* flag, int* log_nodes, int* log_counts,
+    const int* log_len, const float* req, float* used, float* queue_alloc,
+    int* placed, int* job_placed, const int* __restrict__ dom_of,
+    int* __restrict__ dom_count, int D, int N, int R)
+{
+    if (!*flag) {
+        const int len = *log_len;
+        for (int e = threadIdx.x; e < len; e += blockDim.x) {
+            int cnt = log_counts[e];
+            if (cnt == 0) continue;
+            int d = dom_of[log_nodes[e]];
+            if (d >= 0 && d < D) atomicSub(dom_count + d, cnt);
+        }
+    }
+    __syncthreads();
+    dev_cond_revert(flag, log_nodes, log_counts, log_len, req, used,
+                    queue_alloc, placed, job_placed, N, R);
+}
+
+// ---------------------------------------------------------------------------
 // Megacycle: a WHOLE small-class plan in ONE launch.  Heterogeneous
 // inventories produce thousands of per-job classes; at ~2 enqueues per
 // class the cycle becomes launch-bound.  This kernel sequences the
@@ -1209,6 +1486,35 @@ void vamd_cond_revert(
     hipLaunchKernelGGL(vamd::cond_revert_kernel, dim3(1), dim3(1024), 0,
                        stream, flag, log_nodes, log_counts, log_len, req,
                        used, queue_alloc, placed, job_placed, N, R);
+}
+
+void vamd_spread_select(
+    float* score, int* cap, const float* req, int ntasks, float* used,
+    float* queue_alloc, const float* queue_limit, int* log_nodes,
+    int* log_counts, int* log_len, int* placed, int* job_placed,
+    const int* dom_of, int* dom_count, int D, int max_skew, int fuse_min,
+    void* scratch, int N, int R, int K, hipStream_t stream)
+{
+    // scratch: D 64-bit head keys, then N log-slot ints
+    unsigned long long* head = (unsigned long long*)scratch;
+    int* slot = (int*)(head + (D > 0 ? D : 0));
+    hipLaunchKernelGGL(vamd::spread_select_kernel, dim3(1), dim3(SP_THREADS),
+                       0, stream, score, cap, req, ntasks, used, queue_alloc,
+                       queue_limit, log_nodes, log_counts, log_len, placed,
+                       job_placed, dom_of, dom_count, D, max_skew, fuse_min,
+                       head, slot, N, R, K);
+}
+
+void vamd_spread_revert(
+    const uint8_t* flag, int* log_nodes, int* log_counts, const int* log_len,
+    const float* req, float* used, float* queue_alloc, int* placed,
+    int* job_placed, const int* dom_of, int* dom_count, int D, int N, int R,
+    hipStream_t stream)
+{
+    hipLaunchKernelGGL(vamd::spread_revert_kernel, dim3(1), dim3(1024), 0,
+                       stream, flag, log_nodes, log_counts, log_len, req,
+                       used, queue_alloc, placed, job_placed, dom_of,
+                       dom_count, D, N, R);
 }
 
 void vamd_batch_score(

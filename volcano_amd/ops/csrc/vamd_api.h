@@ -42,6 +42,27 @@ void vamd_cond_revert(
     const float* req, float* used, float* queue_alloc, int* placed,
     int* job_placed, int N, int R, hipStream_t stream);
 
+// Topology-spread select (after vamd_score_cap; ONE workgroup): maxSkew is
+// checked before every single placement against the group's live
+// per-domain counts.  `score` and `cap` are consumed.  `scratch` holds
+// 8*D + 4*N bytes, 8-byte aligned.  D in [1, N]; dom_of[n] in [-1, D).
+void vamd_spread_select(
+    float* score, int* cap, const float* req, int ntasks, float* used,
+    float* queue_alloc, const float* queue_limit, int* log_nodes,
+    int* log_counts, int* log_len, int* placed, int* job_placed,
+    const int* dom_of,       // [N] node -> domain id, -1 = no label
+    int* dom_count,          // [D] group members per domain, in place
+    int D, int max_skew, int fuse_min,
+    void* scratch, int N, int R, int K, hipStream_t stream);
+
+// vamd_cond_revert for a spread class: also takes the logged placements
+// back out of dom_count.
+void vamd_spread_revert(
+    const uint8_t* flag, int* log_nodes, int* log_counts, const int* log_len,
+    const float* req, float* used, float* queue_alloc, int* placed,
+    int* job_placed, const int* dom_of, int* dom_count, int D, int N, int R,
+    hipStream_t stream);
+
 // --- whole-cycle runner ----------------------------------------------------
 
 // One task class (a batch of identical pending tasks of one job).
@@ -149,6 +170,37 @@ void vamd_run_cycle(
     uint8_t* job_flag,             // [J]
     unsigned* sort_scratch,        // [4N] bulk-select radix scratch (nullable)
     int N, int R, int W,
+    hipStream_t stream);
+
+// vamd_run_cycle for plans with topology-spread classes.  A spread class
+// (class_spread_group[c] >= 0) always runs vamd_score_cap +
+// vamd_spread_select — never the fused, bulk, chain or megacycle path —
+// and reverts through vamd_spread_revert.  Counts carry across the
+// classes of a group in plan order and stay on the device.  With
+// class_spread_group == nullptr (or all -1) this IS vamd_run_cycle:
+// the same launches in the same order.
+void vamd_run_cycle_spread(
+    const VamdClassDesc* classes, int n_classes,
+    const VamdJobDesc* jobs, int n_jobs,
+    const float* alloc, float* used, const float* extra,
+    const uint8_t* ready, const int64_t* taints, const int64_t* planes,
+    const float* bias, const float* bias_rows,
+    const float* class_req, const int64_t* class_tol,
+    const int64_t* class_require, const int64_t* class_forbid,
+    const int32_t* class_min, const float* dim_w,
+    float* queue_alloc, const float* queue_limit,
+    float* score_scratch, int* cap_scratch,
+    int* log_nodes, int* log_counts, int* log_len,
+    int* class_placed, int* job_placed, uint8_t* job_flag,
+    unsigned* sort_scratch,
+    int N, int R, int W,
+    const int32_t* class_spread_group,  // HOST [C]: group index or -1
+    const int32_t* class_spread_skew,   // HOST [C]: maxSkew (>= 1)
+    const int32_t* spread_dom_of,       // device [G, N]
+    int32_t* spread_count,              // device, groups back to back
+    const int32_t* spread_count_off,    // HOST [G]: offset into spread_count
+    const int32_t* spread_domains,      // HOST [G]: D of each group
+    void* spread_scratch,               // device, 12*N bytes, 8-aligned
     hipStream_t stream);
 
 }  // extern "C"

@@ -56,6 +56,9 @@ def _load():
     lib.vamd_run_cycle.restype = None
     lib.vamd_fused_score_select.restype = None
     lib.vamd_topk.restype = None
+    lib.vamd_spread_select.restype = None
+    lib.vamd_spread_revert.restype = None
+    lib.vamd_run_cycle_spread.restype = None
     _lib = lib
     return lib
 
@@ -127,6 +130,51 @@ def cond_revert(flag, log_nodes, log_counts, log_len, req, used_t,
         c_int(N), c_int(R), _stream())
 
 
+def spread_scratch(N: int, device) -> torch.Tensor:
+    """Scratch of one spread select: D <= N 64-bit head keys + N log-slot
+    ints (torch device allocations are at least 8-byte aligned)."""
+    return torch.empty(3 * max(int(N), 1), dtype=torch.int32, device=device)
+
+
+def spread_select(score, cap, req, ntasks, used_t, queue_alloc_row,
+                  queue_limit_row, log_nodes, log_counts, log_len, placed,
+                  job_placed, dom_of, dom_count, max_skew, fuse_min,
+                  scratch=None):
+    """Topology-spread select (after score_cap): maxSkew checked before
+    every placement.  ``score`` and ``cap`` are consumed."""
+    lib = _load()
+    N = score.shape[0]
+    R = req.shape[0]
+    K = log_nodes.shape[0]
+    D = dom_count.shape[0]
+    if not 1 <= D <= max(N, 1):
+        raise ValueError(f"spread_select: D={D} outside [1, N={N}]")
+    if int(max_skew) < 1:
+        raise ValueError("spread_select: max_skew must be >= 1")
+    if dom_of.shape[0] != N:
+        raise ValueError("spread_select: dom_of must have one entry per node")
+    if scratch is None:
+        scratch = spread_scratch(N, score.device)
+    lib.vamd_spread_select(
+        _p(score), _p(cap), _p(req), c_int(int(ntasks)), _p(used_t),
+        _p(queue_alloc_row), _p(queue_limit_row), _p(log_nodes),
+        _p(log_counts), _p(log_len), _p(placed), _p(job_placed),
+        _p(dom_of), _p(dom_count), c_int(D), c_int(int(max_skew)),
+        c_int(int(fuse_min)), _p(scratch),
+        c_int(N), c_int(R), c_int(K), _stream())
+
+
+def spread_revert(flag, log_nodes, log_counts, log_len, req, used_t,
+                  queue_alloc_row, placed, job_placed, dom_of, dom_count):
+    lib = _load()
+    R, N = used_t.shape
+    lib.vamd_spread_revert(
+        _p(flag), _p(log_nodes), _p(log_counts), _p(log_len), _p(req),
+        _p(used_t), _p(queue_alloc_row), _p(placed), _p(job_placed),
+        _p(dom_of), _p(dom_count), c_int(dom_count.shape[0]),
+        c_int(N), c_int(R), _stream())
+
+
 def fused_score_select(alloc_t, used_t, extra_t, ready, taints, planes_t,
                        req, tolerated, require, forbid, w_least, w_most,
                        w_bal, dim_w, bias, score, cap, ntasks,
@@ -165,11 +213,36 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
               bias, bias_rows, class_req, class_tol, class_require,
               class_forbid, class_min, dim_w, queue_alloc, queue_limit,
               score_scratch, cap_scratch, log_nodes, log_counts, log_len,
-              class_placed, job_placed, job_flag, sort_scratch=None):
-    """One library call = one whole allocate cycle (plan built host-side)."""
+              class_placed, job_placed, job_flag, sort_scratch=None,
+              spread=None):
+    """One library call = one whole allocate cycle (plan built host-side).
+
+    ``spread`` (plans with topology-spread classes only) is a dict:
+    ``class_group``/``class_skew`` host int32 numpy [C], ``dom_of`` device
+    i32 [G, N], ``count`` device i32 (groups back to back), ``count_off``/
+    ``domains`` host int32 numpy [G], ``scratch`` device
+    (``spread_scratch``)."""
     lib = _load()
     R, N = alloc_t.shape
     W = planes_t.shape[0]
+    if spread is not None:
+        lib.vamd_run_cycle_spread(
+            class_descs, c_int(n_classes),
+            job_descs, c_int(n_jobs),
+            _p(alloc_t), _p(used_t), _p(extra_t), _p(ready), _p(taints),
+            _p(planes_t), _p(bias), _p(bias_rows), _p(class_req),
+            _p(class_tol), _p(class_require), _p(class_forbid),
+            _p(class_min), _p(dim_w), _p(queue_alloc), _p(queue_limit),
+            _p(score_scratch), _p(cap_scratch), _p(log_nodes),
+            _p(log_counts), _p(log_len), _p(class_placed), _p(job_placed),
+            _p(job_flag), _p(sort_scratch), c_int(N), c_int(R), c_int(W),
+            c_void_p(spread["class_group"].ctypes.data),
+            c_void_p(spread["class_skew"].ctypes.data),
+            _p(spread["dom_of"]), _p(spread["count"]),
+            c_void_p(spread["count_off"].ctypes.data),
+            c_void_p(spread["domains"].ctypes.data),
+            _p(spread["scratch"]), _stream())
+        return
     lib.vamd_run_cycle(
         class_descs, c_int(n_classes),
         job_descs, c_int(n_jobs),

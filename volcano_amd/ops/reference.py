@@ -18,6 +18,8 @@ Kernel inventory (SURVEY.md §2.9 K1–K6 mapping):
 * ``select_commit``  — K2 select + K4 gang placement with undo log.
 * ``finalize_job``   — K4 gang readiness decision (device flag).
 * ``cond_revert``    — K4 rollback of one class, gated on the job flag.
+* ``spread_select_commit`` / ``spread_revert`` — K2 select under a
+  topology-spread bound checked before every placement, and its rollback.
 * ``drf_share``      — K3 dominant share per job.
 * ``waterfill``      — K3 proportion/capacity deserved water-filling.
 
@@ -186,6 +188,115 @@ def cond_revert(
     job_placed.add_((-placed * (flag == 0).to(torch.int32)))
     placed.mul_((flag != 0).to(torch.int32))
     log_counts.mul_((flag != 0).to(torch.int32))
+
+
+def spread_select_commit(
+    score: torch.Tensor,        # [N] f32 from score_cap
+    cap: torch.Tensor,          # [N] i32
+    req: torch.Tensor,          # [R] f32
+    ntasks: int,
+    used: torch.Tensor,         # [N, R] f32 — updated in place (staged)
+    queue_alloc: torch.Tensor,  # [R] f32 in place
+    queue_limit: torch.Tensor,  # [R] f32
+    log_nodes: torch.Tensor,    # [K] i32 (K ≥ min(ntasks, N))
+    log_counts: torch.Tensor,   # [K] i32
+    log_len: torch.Tensor,      # [] i32
+    placed: torch.Tensor,       # [] i32
+    job_placed: torch.Tensor,   # [] i32
+    dom_of: torch.Tensor,       # [N] i32 node → spread domain (-1: unlabeled)
+    dom_count: torch.Tensor,    # [D] i32 group members per domain, in place
+    max_skew: int,              # ≥ 1
+) -> None:
+    """Per-placement topology-spread fill for one task class (k8s
+    podtopologyspread DoNotSchedule, evaluated before EVERY instance).
+
+    A plain sequential loop on purpose — this is the source of truth the
+    HIP ``spread_select_kernel`` must reproduce bit for bit.  Scores are
+    static within the class (as in ``select_commit``); what changes after
+    each placement is eligibility: a node may take an instance only while
+    ``dom_count[its domain] + 1 - min(dom_count) <= max_skew``.  The
+    minimum ranges over ALL domains, also those without a feasible node.
+    Counts only change on placement, so a state with no eligible node is
+    final and the loop stops there.
+
+    The log carries one (node, count) entry per node in order of first
+    placement; ``used`` takes one ``float(count) * req`` per entry.
+    """
+    if max_skew < 1:
+        raise ValueError("max_skew must be >= 1")
+    N = score.shape[0]
+    log_nodes.zero_()
+    log_counts.zero_()
+
+    headroom = queue_limit - queue_alloc
+    pos = req > EPS
+    per_dim = torch.where(pos, (headroom + EPS) / torch.clamp(req, min=EPS),
+                          torch.full_like(headroom, float(BIG_CAP)))
+    quota = int(per_dim.amin().clamp(min=0, max=float(BIG_CAP)).floor())
+    budget = min(int(ntasks), quota)
+
+    sc = score.tolist()
+    dom = dom_of.tolist()
+    cnt = dom_count.tolist()
+    rem = [int(c) if (s > NEG_INF and d >= 0) else 0
+           for s, c, d in zip(sc, cap.tolist(), dom)]
+    slot = {}                   # node → log entry
+    nodes: list = []
+    counts: list = []
+    total = 0
+    while total < budget:
+        m = min(cnt)
+        best = -1
+        for n in range(N):
+            if rem[n] > 0 and cnt[dom[n]] + 1 - m <= max_skew \
+                    and (best < 0 or sc[n] > sc[best]):
+                best = n
+        if best < 0:
+            break
+        rem[best] -= 1
+        cnt[dom[best]] += 1
+        total += 1
+        e = slot.get(best)
+        if e is None:
+            slot[best] = len(nodes)
+            nodes.append(best)
+            counts.append(1)
+        else:
+            counts[e] += 1
+
+    m = len(nodes)
+    assert m <= log_nodes.shape[0], "undo-log slot too small"
+    dev = score.device
+    idx = torch.tensor(nodes, dtype=torch.long, device=dev)
+    c32 = torch.tensor(counts, dtype=torch.int32, device=dev)
+    log_nodes[:m] = idx.to(torch.int32)
+    log_counts[:m] = c32
+    log_len.fill_(m)
+    dom_count.copy_(torch.tensor(cnt, dtype=torch.int32, device=dev))
+    used.index_add_(0, idx, c32.to(torch.float32).unsqueeze(1)
+                    * req.unsqueeze(0))
+    queue_alloc += torch.tensor(float(total), device=dev) * req
+    placed.fill_(total)
+    job_placed.add_(total)
+
+
+def spread_revert(
+    flag: torch.Tensor, log_nodes: torch.Tensor, log_counts: torch.Tensor,
+    log_len: torch.Tensor, req: torch.Tensor, used: torch.Tensor,
+    queue_alloc: torch.Tensor, placed: torch.Tensor,
+    job_placed: torch.Tensor,
+    dom_of: torch.Tensor,       # [N] i32
+    dom_count: torch.Tensor,    # [D] i32 in place
+) -> None:
+    """``cond_revert`` for a spread class: additionally gives the logged
+    placements back to the group's per-domain counts."""
+    if int(flag) == 0:
+        n = int(log_len)
+        nodes = log_nodes[:n].to(torch.long)
+        doms = dom_of[nodes].to(torch.long)
+        dom_count.index_add_(0, doms, -log_counts[:n])
+    cond_revert(flag, log_nodes, log_counts, log_len, req, used,
+                queue_alloc, placed, job_placed)
 
 
 def drf_share(job_alloc: torch.Tensor, total: torch.Tensor) -> torch.Tensor:

@@ -232,6 +232,39 @@ class AllocateAction:
                     out = b if out is None else out + b
             return out
 
+        # exact topology spread (topologyspread plugin, ``exact: true``):
+        # matching classes go through the per-placement spread select.
+        # Not under the soft-shard coordinator, whose conflict reconcile
+        # can drop placements the kernel already counted.
+        spread_exact = getattr(ssn, "spread_exact", None) \
+            if self.coordinator is None else None
+        spread_group_of: Dict[int, int] = {}   # plugin group → plan group
+
+        def spread_attach(cp: ClassPlan, sp) -> None:
+            """Route cp through the spread select; its constraint words
+            lose the session-open saturation bit (the memoized arrays are
+            shared with the cycle-granular consumers — copy first)."""
+            g, skew = sp
+            pg = spread_group_of.get(g)
+            if pg is None:
+                pg = spread_group_of[g] = plan.add_spread_group(
+                    spread_exact.dom_of[g], spread_exact.count[g])
+            cp.spread = (pg, skew)
+            bit = spread_exact.sat_bit[g]
+            if bit is not None and bit // 64 < len(cp.forbid):
+                cp.forbid = cp.forbid.copy()
+                cp.forbid[bit // 64] &= ~(np.int64(1) << np.int64(bit % 64))
+
+        # such jobs never join a fused signature run
+        if spread_exact is not None and elig_l is not None:
+            for ix, jb in enumerate(jobs_l):
+                if elig_l[ix]:
+                    t0_ = next(iter(jb.task_status_index.get(
+                        _TS.PENDING, {}).values()), None)
+                    if t0_ is not None and \
+                            spread_exact.resolve_task(t0_) is not None:
+                        elig_l[ix] = False
+
         # nominated gangs take the host fast path — exclude them from runs
         if elig_l is not None and self.coordinator is None and \
                 getattr(ssn.cache, "had_nominations", False):
@@ -352,7 +385,9 @@ class AllocateAction:
                 # TaskClass/ClassPlan/constraint work bundle_in would
                 # discard anyway (dominant shape: thousands of identical
                 # gangs back to back)
-                if not bias_fns and open_bundle is not None \
+                sp = spread_exact.resolve_task(first) \
+                    if spread_exact is not None else None
+                if sp is None and not bias_fns and open_bundle is not None \
                         and open_key == (qi, sig):
                     tasks = list(pend.values())
                     mtm = job._mtm
@@ -404,7 +439,10 @@ class AllocateAction:
                                w_least=w_least, w_most=w_most, w_bal=w_bal)
                 if bias_fns:
                     cp.bias = class_bias(tc, job)
-                if cp.bias is not None:     # biased classes never fuse
+                if sp is not None:
+                    spread_attach(cp, sp)
+                # biased and spread classes never fuse
+                if cp.bias is not None or cp.spread is not None:
                     close_bundle()
                     plan.add_job(job, [cp])
                 else:
@@ -436,6 +474,10 @@ class AllocateAction:
                     w_most=w.get("most", 0.0), w_bal=w.get("bal", 0.0))
                 if bias_fns:
                     cp.bias = class_bias(tc, job)
+                if spread_exact is not None:
+                    sp = spread_exact.resolve_task(tc.tasks[0])
+                    if sp is not None:
+                        spread_attach(cp, sp)
                 classes.append(cp)
             if skipped and classes and job.min_available > sum(
                     c.tclass.count for c in classes) + job.occupied_count:
@@ -446,7 +488,8 @@ class AllocateAction:
 
             bundleable = (len(classes) == 1 and job.occupied_count == 0
                           and classes[0].tclass.count == len(job.tasks)
-                          and classes[0].bias is None)
+                          and classes[0].bias is None
+                          and classes[0].spread is None)
             if bundleable:
                 cp = classes[0]
                 gang_min = max(job.min_available, cp.min_needed)

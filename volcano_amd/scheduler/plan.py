@@ -54,6 +54,17 @@ class BundleEntry:
 
 
 @dataclass(slots=True)
+class SpreadGroup:
+    """One topology-spread group of a cycle: the node → domain map and the
+    group's member count per domain at cycle start.  The runners keep the
+    live counts on the device for the whole cycle (every class of the
+    group, in plan order, sees its predecessors' placements and reverts);
+    nothing is read back — the next session recounts from task statuses."""
+    dom_of: np.ndarray         # [N] i32, -1 = node lacks the topology label
+    count: np.ndarray          # [D] i32, 1 <= D <= N
+
+
+@dataclass(slots=True)
 class ClassPlan:
     tclass: TaskClass
     job_key: str
@@ -83,6 +94,10 @@ class ClassPlan:
     # recycling).  The kernel-side fuse_min is the EASIEST entry's
     # minimum: if even that gang can't place, the bundle reverts in-kernel.
     bundle: Optional[List[BundleEntry]] = None
+    # (index into CyclePlan.spread_groups, maxSkew >= 1): the class is
+    # placed by the per-placement topology-spread select instead of
+    # select_commit.  Never combined with ``bundle``.
+    spread: Optional[Tuple[int, int]] = None
 
     @property
     def ntasks(self) -> int:
@@ -168,6 +183,23 @@ class CyclePlan:
         self.bias: Optional[torch.Tensor] = None
         self.dim_w = torch.ones(nt.r, dtype=torch.float32)
         self.log_total = 0
+        self.spread_groups: List[SpreadGroup] = []
+        # live per-domain counts of the last run (device tensors, one per
+        # group) — left for inspection, never copied to the host here
+        self.spread_counts = None
+
+    def add_spread_group(self, dom_of, count) -> int:
+        dom_of = np.ascontiguousarray(dom_of, dtype=np.int32)
+        count = np.ascontiguousarray(count, dtype=np.int32)
+        if dom_of.shape != (self.nt.n,):
+            raise ValueError("spread group: dom_of needs one entry per node")
+        if not 1 <= count.shape[0] <= max(self.nt.n, 1):
+            raise ValueError("spread group: domain count outside [1, N]")
+        if dom_of.max(initial=-1) >= count.shape[0] or \
+                dom_of.min(initial=0) < -1:
+            raise ValueError("spread group: domain id out of range")
+        self.spread_groups.append(SpreadGroup(dom_of, count))
+        return len(self.spread_groups) - 1
 
     def add_job(self, job: JobInfo, classes: List[ClassPlan]) -> None:
         if not classes:
@@ -215,6 +247,15 @@ class CyclePlan:
             if len(cp.forbid) < W:
                 cp.forbid = np.pad(cp.forbid, (0, W - len(cp.forbid)))
             self.req_np[c] = cp.req
+            if cp.spread is not None:
+                g, skew = cp.spread
+                if not 0 <= g < len(self.spread_groups):
+                    raise ValueError(f"class {c}: unknown spread group {g}")
+                if skew < 1:
+                    raise ValueError(f"class {c}: maxSkew must be >= 1")
+                if cp.bundle is not None:
+                    raise ValueError(f"class {c}: spread classes never "
+                                     "bundle")
         self.log_total = off
         lens = np.fromiter((jp.class_end - jp.class_begin
                             for jp in self.jobs), dtype=np.int64,
@@ -254,6 +295,24 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
     job_flag = torch.ones(len(plan.jobs), dtype=torch.uint8, device=dev)
     class_min = torch.tensor([cp.min_needed for cp in plan.classes],
                              dtype=torch.int32, device=dev)
+    sp_dom = [torch.from_numpy(g.dom_of).to(dev) for g in plan.spread_groups]
+    sp_cnt = [torch.from_numpy(g.count.copy()).to(dev)
+              for g in plan.spread_groups]
+    plan.spread_counts = sp_cnt
+
+    def revert(c, cp, flag, req, sl):
+        if cp.spread is not None:
+            g = cp.spread[0]
+            ref.spread_revert(flag, log_nodes[sl], log_counts[sl],
+                              log_len[c], req, used,
+                              plan.queue_alloc[cp.queue_idx],
+                              class_placed[c], job_placed[j],
+                              sp_dom[g], sp_cnt[g])
+        else:
+            ref.cond_revert(flag, log_nodes[sl], log_counts[sl],
+                            log_len[c], req, used,
+                            plan.queue_alloc[cp.queue_idx],
+                            class_placed[c], job_placed[j])
 
     for j, jp in enumerate(plan.jobs):
         nc = jp.class_end - jp.class_begin
@@ -271,20 +330,27 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
                           cp.w_least, cp.w_most, cp.w_bal, dim_w, b,
                           score, cap)
             sl = slice(cp.log_off, cp.log_off + cp.log_cap)
-            ref.select_commit(score, cap, req, cp.ntasks, used,
-                              plan.queue_alloc[cp.queue_idx],
-                              plan.queue_limit[cp.queue_idx],
-                              log_nodes[sl], log_counts[sl], log_len[c],
-                              class_placed[c], job_placed[j])
+            if cp.spread is not None:
+                g, skew = cp.spread
+                ref.spread_select_commit(
+                    score, cap, req, cp.ntasks, used,
+                    plan.queue_alloc[cp.queue_idx],
+                    plan.queue_limit[cp.queue_idx],
+                    log_nodes[sl], log_counts[sl], log_len[c],
+                    class_placed[c], job_placed[j],
+                    sp_dom[g], sp_cnt[g], skew)
+            else:
+                ref.select_commit(score, cap, req, cp.ntasks, used,
+                                  plan.queue_alloc[cp.queue_idx],
+                                  plan.queue_limit[cp.queue_idx],
+                                  log_nodes[sl], log_counts[sl], log_len[c],
+                                  class_placed[c], job_placed[j])
             if single:
                 need = max(jp.min_available - jp.occupied, cp.min_needed, 0)
                 flag = (class_placed[c] >= need).to(torch.uint8)
                 job_flag[j] = flag
                 if int(flag) == 0:
-                    ref.cond_revert(flag, log_nodes[sl], log_counts[sl],
-                                    log_len[c], req, used,
-                                    plan.queue_alloc[cp.queue_idx],
-                                    class_placed[c], job_placed[j])
+                    revert(c, cp, flag, req, sl)
         if not single:
             ref.finalize_job(job_placed[j], jp.occupied, jp.min_available,
                              class_placed[jp.class_begin:jp.class_end],
@@ -294,10 +360,7 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
                 cp = plan.classes[c]
                 req = torch.from_numpy(cp.req).to(dev)
                 sl = slice(cp.log_off, cp.log_off + cp.log_cap)
-                ref.cond_revert(job_flag[j], log_nodes[sl], log_counts[sl],
-                                log_len[c], req, used,
-                                plan.queue_alloc[cp.queue_idx],
-                                class_placed[c], job_placed[j])
+                revert(c, cp, job_flag[j], req, sl)
 
     return CycleResult(plan, log_nodes.cpu().numpy(),
                       log_counts.cpu().numpy(), log_len.cpu().numpy(),
@@ -389,6 +452,31 @@ def run_plan_hip(plan: CyclePlan) -> CycleResult:
     sort_scratch = torch.empty(4 * N, dtype=torch.int32, device=dev) \
         if C and int(cds["ntasks"].max()) >= 512 and N >= 512 else None
 
+    # topology-spread classes: group tables go to the device once, the
+    # per-class (group, maxSkew) columns stay host-side for the runner
+    spread = None
+    if any(cp.spread is not None for cp in plan.classes):
+        groups = plan.spread_groups
+        cg = np.full(C, -1, dtype=np.int32)
+        cs = np.ones(C, dtype=np.int32)
+        for c, cp in enumerate(plan.classes):
+            if cp.spread is not None:
+                cg[c], cs[c] = cp.spread
+        doms = np.array([g.count.shape[0] for g in groups], dtype=np.int32)
+        offs = (np.cumsum(doms) - doms).astype(np.int32)
+        count = torch.from_numpy(
+            np.concatenate([g.count for g in groups]).astype(np.int32)
+        ).to(dev)
+        spread = dict(
+            class_group=cg, class_skew=cs,
+            dom_of=torch.from_numpy(
+                np.stack([g.dom_of for g in groups]).astype(np.int32)
+            ).to(dev).contiguous(),
+            count=count, count_off=offs, domains=doms,
+            scratch=hip.spread_scratch(N, dev))
+        plan.spread_counts = [count[int(o):int(o) + int(d)]
+                              for o, d in zip(offs, doms)]
+
     hip.run_cycle(
         ctypes.c_void_p(cds.ctypes.data), C,
         ctypes.c_void_p(jds.ctypes.data), len(plan.jobs),
@@ -396,7 +484,7 @@ def run_plan_hip(plan: CyclePlan) -> CycleResult:
         nt.planes_t, bias, bias_rows, class_req, class_tol, class_require,
         class_forbid, class_min, dim_w, q_alloc, q_limit, score, cap,
         log_nodes, log_counts, log_len, class_placed, job_placed, job_flag,
-        sort_scratch)
+        sort_scratch, spread=spread)
 
     res = CycleResult(plan, log_nodes.cpu().numpy(),
                       log_counts.cpu().numpy(), log_len.cpu().numpy(),
