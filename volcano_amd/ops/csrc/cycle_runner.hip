@@ -28,11 +28,13 @@ static bool megacycle_enabled() {
     return e != nullptr && atoi(e) != 0;
 }
 
-// Spread classes of a plan (host-side view; all null when the plan has
-// none, and then nothing below changes a single launch).
+// Domain-rule classes of a plan — topology spread and inter-pod
+// (anti-)affinity share the group tables (host-side view; all null when
+// the plan has none, and then nothing below changes a single launch).
 struct SpreadArgs {
     const int32_t* group = nullptr;      // [C] group index or -1
     const int32_t* skew = nullptr;       // [C]
+    const int32_t* mode = nullptr;       // [C] 0 spread / 1 affinity / 2 anti
     const int32_t* dom_of = nullptr;     // device [G, N]
     int32_t* count = nullptr;            // device, flat
     const int32_t* count_off = nullptr;  // [G]
@@ -244,6 +246,39 @@ static void run_cycle_impl(
             }
 
             const int g = spread_of(c);
+            const int dmode = (g >= 0 && sp.mode != nullptr) ? sp.mode[c] : 0;
+            if (g >= 0 && dmode != 0) {
+                // inter-pod affinity / keyed anti-affinity: the rule
+                // collapses into a mask over score/cap computed from the
+                // group's live counts, then the ordinary select (bulk by
+                // size) and one count update — four launches whatever
+                // ntasks is
+                vamd_score_cap(alloc, used, ext, ready, taints, planes,
+                               class_req + (size_t)c * R, class_tol[c],
+                               class_require + (size_t)c * W,
+                               class_forbid + (size_t)c * W,
+                               cd.w_least, cd.w_most, cd.w_bal, dim_w, b,
+                               score_scratch, cap_scratch, N, R, W, stream);
+                vamd_domain_mask(score_scratch, cap_scratch,
+                                 sp.dom_of + (size_t)g * N,
+                                 sp.count + sp.count_off[g], sp.domains[g],
+                                 dmode, sp.scratch, N, stream);
+                vamd_select_commit(score_scratch, cap_scratch,
+                                   class_req + (size_t)c * R, cd.ntasks, used,
+                                   queue_alloc + (size_t)cd.queue_idx * R,
+                                   queue_limit + (size_t)cd.queue_idx * R,
+                                   log_nodes + cd.log_off,
+                                   log_counts + cd.log_off,
+                                   log_len + c, class_placed + c,
+                                   job_placed + j, fuse_min, sort_scratch,
+                                   N, R, cd.log_cap, stream);
+                vamd_domain_count_add(log_nodes + cd.log_off,
+                                      log_counts + cd.log_off, log_len + c,
+                                      sp.dom_of + (size_t)g * N,
+                                      sp.count + sp.count_off[g],
+                                      sp.domains[g], N, cd.log_cap, stream);
+                continue;
+            }
             if (g >= 0) {
                 // topology spread: eligibility moves with every single
                 // placement — always score + spread select, whatever the
@@ -390,6 +425,48 @@ extern "C" void vamd_run_cycle_spread(
             spread_count != nullptr && spread_scratch != nullptr) {
         sp.group = class_spread_group;
         sp.skew = class_spread_skew;
+        sp.dom_of = spread_dom_of;
+        sp.count = spread_count;
+        sp.count_off = spread_count_off;
+        sp.domains = spread_domains;
+        sp.scratch = spread_scratch;
+    }
+    run_cycle_impl(classes, n_classes, jobs, n_jobs, alloc, used, extra,
+                   ready, taints, planes, bias, bias_rows, class_req,
+                   class_tol, class_require, class_forbid, class_min, dim_w,
+                   queue_alloc, queue_limit, score_scratch, cap_scratch,
+                   log_nodes, log_counts, log_len, class_placed, job_placed,
+                   job_flag, sort_scratch, N, R, W, sp, stream);
+}
+
+extern "C" void vamd_run_cycle_domains(
+    const VamdClassDesc* classes, int n_classes,
+    const VamdJobDesc* jobs, int n_jobs,
+    const float* alloc, float* used, const float* extra,
+    const uint8_t* ready, const int64_t* taints, const int64_t* planes,
+    const float* bias,
+    const float* bias_rows,
+    const float* class_req, const int64_t* class_tol,
+    const int64_t* class_require, const int64_t* class_forbid,
+    const int32_t* class_min, const float* dim_w,
+    float* queue_alloc, const float* queue_limit,
+    float* score_scratch, int* cap_scratch,
+    int* log_nodes, int* log_counts, int* log_len,
+    int* class_placed, int* job_placed, uint8_t* job_flag,
+    unsigned* sort_scratch,
+    int N, int R, int W,
+    const int32_t* class_spread_group, const int32_t* class_spread_skew,
+    const int32_t* class_domain_mode,
+    const int32_t* spread_dom_of, int32_t* spread_count,
+    const int32_t* spread_count_off, const int32_t* spread_domains,
+    void* spread_scratch, hipStream_t stream)
+{
+    SpreadArgs sp;
+    if (class_spread_group != nullptr && spread_dom_of != nullptr &&
+            spread_count != nullptr && spread_scratch != nullptr) {
+        sp.group = class_spread_group;
+        sp.skew = class_spread_skew;
+        sp.mode = class_domain_mode;
         sp.dom_of = spread_dom_of;
         sp.count = spread_count;
         sp.count_off = spread_count_off;

@@ -978,6 +978,148 @@ __global__ void spread_revert_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Inter-pod (anti-)affinity over a topology key, enforced before EVERY
+// placement — oracle: reference.py affinity_select_commit.  Unlike spread
+// this needs no per-instance loop: for both modes the per-placement rule
+// collapses into a static mask over score/cap, computed once per class
+// from the live per-domain counts, after which the ordinary select_commit
+// (serial or bulk) yields the sequential result, log order included.
+//
+//   * affinity: placing into an eligible domain never changes the eligible
+//     set; only the anchor (first member of an empty group) does.  So:
+//     hosting = #domains with count > 0 (counts are >= 0 — every revert
+//     takes back exactly what its own log added — so this is zero iff the
+//     sum of the counts is); if 0, the anchor is the domain of
+//     the block argmax over placeable nodes (ties -> lower index); every
+//     node of a domain that is neither hosting nor the anchor is masked.
+//   * anti: "best eligible node, then its domain closes" repeated equals
+//     "the best node of each open domain, capacity 1, in score order".
+//     Heads are 64-bit keys as in spread_select_kernel (atomicMax behind a
+//     filtering read, only for domains with count == 0); a node stays iff
+//     its key is its domain's head.
+//
+// A masked node gets score = -inf AND cap = 0; a kept node always has
+// score > -inf, cap > 0 and 0 <= dom < D.  ONE workgroup: the argmax and
+// the heads need a block-wide result before the mask pass, and a class's
+// score vector is L2-resident (4 B/node).  Barriers sit only under
+// block-uniform conditions (mode is a launch argument, s_hosting is read
+// after a barrier); thread 0 publishes the anchor.
+// `head` is D 64-bit words of scratch (anti mode only).
+// ---------------------------------------------------------------------------
+#define DM_AFFINITY 1
+#define DM_ANTI 2
+
+__global__ void __launch_bounds__(SP_THREADS)
+domain_mask_kernel(
+    float* __restrict__ score,            // [N] in place
+    int* __restrict__ cap,                // [N] in place
+    const int* __restrict__ dom_of,       // [N] domain id, -1 = unlabeled
+    const int* __restrict__ dom_count,    // [D]
+    int D, int mode,
+    unsigned long long* __restrict__ head,  // [D] scratch (anti)
+    int N)
+{
+    __shared__ ValIdx s_wave[SP_WAVES];
+    __shared__ int s_wint[SP_WAVES];
+    __shared__ int s_hosting;
+    __shared__ int s_anchor;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wid = tid / WAVE;
+
+    if (mode == DM_AFFINITY) {
+        int h = 0;
+        for (int d = tid; d < D; d += SP_THREADS)
+            h += dom_count[d] > 0 ? 1 : 0;
+        for (int off = WAVE / 2; off > 0; off >>= 1)
+            h += __shfl_down(h, off);
+        if (lane == 0) s_wint[wid] = h;
+        __syncthreads();
+        if (tid == 0) {
+            int t = 0;
+            for (int w = 0; w < SP_WAVES; ++w) t += s_wint[w];
+            s_hosting = t;
+            s_anchor = -1;
+        }
+        __syncthreads();
+        const bool need_anchor = s_hosting == 0;    // block-uniform
+        if (need_anchor) {
+            ValIdx loc; loc.v = NEG_INF; loc.i = INT32_MAX;
+            for (int i = tid; i < N; i += SP_THREADS) {
+                const int d = dom_of[i];
+                if (d >= 0 && d < D && cap[i] > 0) {
+                    ValIdx c; c.v = score[i]; c.i = i;
+                    loc = better(loc, c);
+                }
+            }
+            ValIdx w = wave_reduce(loc);
+            if (lane == 0) s_wave[wid] = w;
+            __syncthreads();
+            if (wid == 0) {
+                ValIdx b; b.v = NEG_INF; b.i = INT32_MAX;
+                if (lane < SP_WAVES) b = s_wave[lane];
+                b = wave_reduce(b);
+                if (lane == 0)
+                    s_anchor = (b.v != NEG_INF && b.i >= 0 && b.i < N)
+                        ? dom_of[b.i] : -1;
+            }
+            __syncthreads();
+        }
+        const int anchor = s_anchor;
+        for (int i = tid; i < N; i += SP_THREADS) {
+            const int d = dom_of[i];
+            bool keep = d >= 0 && d < D && cap[i] > 0 && score[i] > NEG_INF;
+            if (keep) keep = dom_count[d] > 0 || d == anchor;
+            if (!keep) { score[i] = NEG_INF; cap[i] = 0; }
+        }
+        return;
+    }
+
+    // anti-affinity: one head per open domain
+    for (int d = tid; d < D; d += SP_THREADS) head[d] = 0ull;
+    __syncthreads();
+    for (int i = tid; i < N; i += SP_THREADS) {
+        const int d = dom_of[i];
+        const float s = score[i];
+        if (d >= 0 && d < D && cap[i] > 0 && s > NEG_INF
+                && dom_count[d] == 0)
+            head_offer(head + d, spread_key(s, i));
+    }
+    __syncthreads();
+    for (int i = tid; i < N; i += SP_THREADS) {
+        const int d = dom_of[i];
+        const float s = score[i];
+        bool keep = d >= 0 && d < D && cap[i] > 0 && s > NEG_INF
+            && dom_count[d] == 0;
+        if (keep) keep = head_load(head + d) == spread_key(s, i);
+        if (keep) cap[i] = 1;
+        else { score[i] = NEG_INF; cap[i] = 0; }
+    }
+}
+
+// After the select of an affinity / anti-affinity class: the logged
+// placements join the group's per-domain counts.  Integer atomics — log
+// entries can share a domain.  A fused gang revert leaves zeroed counts in
+// the log, so it adds nothing.
+__global__ void domain_count_add_kernel(
+    const int* __restrict__ log_nodes, const int* __restrict__ log_counts,
+    const int* __restrict__ log_len, const int* __restrict__ dom_of,
+    int* __restrict__ dom_count, int D, int N, int K)
+{
+    int len = *log_len;
+    if (len > K) len = K;
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < len;
+         e += gridDim.x * blockDim.x) {
+        const int cnt = log_counts[e];
+        const int node = log_nodes[e];
+        if (cnt <= 0 || node < 0 || node >= N) continue;
+        const int d = dom_of[node];
+        if (d >= 0 && d < D) atomicAdd(dom_count + d, cnt);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Megacycle: a WHOLE small-class plan in ONE launch.  Heterogeneous
 // inventories produce thousands of per-job classes; at ~2 enqueues per
 // class the cycle becomes launch-bound.  This kernel sequences the
@@ -1515,6 +1657,28 @@ void vamd_spread_revert(
                        stream, flag, log_nodes, log_counts, log_len, req,
                        used, queue_alloc, placed, job_placed, dom_of,
                        dom_count, D, N, R);
+}
+
+void vamd_domain_mask(
+    float* score, int* cap, const int* dom_of, const int* dom_count, int D,
+    int mode, void* scratch, int N, hipStream_t stream)
+{
+    hipLaunchKernelGGL(vamd::domain_mask_kernel, dim3(1), dim3(SP_THREADS),
+                       0, stream, score, cap, dom_of, dom_count, D, mode,
+                       (unsigned long long*)scratch, N);
+}
+
+void vamd_domain_count_add(
+    const int* log_nodes, const int* log_counts, const int* log_len,
+    const int* dom_of, int* dom_count, int D, int N, int K,
+    hipStream_t stream)
+{
+    int threads = 256;
+    int blocks = min((K + threads - 1) / threads, 64);
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(vamd::domain_count_add_kernel, dim3(blocks),
+                       dim3(threads), 0, stream, log_nodes, log_counts,
+                       log_len, dom_of, dom_count, D, N, K);
 }
 
 void vamd_batch_score(

@@ -63,6 +63,27 @@ void vamd_spread_revert(
     int* job_placed, const int* dom_of, int* dom_count, int D, int N, int R,
     hipStream_t stream);
 
+// Inter-pod (anti-)affinity over a topology key, per placement (after
+// vamd_score_cap, before vamd_select_commit; ONE workgroup).  Masks
+// score/cap in place (masked: score = -inf, cap = 0) so that the ordinary
+// select yields the sequential per-instance result.
+//   mode 1, affinity: keep nodes of domains with count > 0; if there is
+//     none, keep the domain of the best placeable node (the anchor).
+//   mode 2, anti-affinity: keep the best node of each domain with
+//     count == 0, with cap 1.
+// Nodes with dom_of < 0 are masked in both modes.  `scratch` holds 8*D
+// bytes, 8-byte aligned (used in mode 2).  D in [1, N].
+void vamd_domain_mask(
+    float* score, int* cap, const int* dom_of, const int* dom_count, int D,
+    int mode, void* scratch, int N, hipStream_t stream);
+
+// dom_count[dom_of[log_nodes[e]]] += log_counts[e] for e < *log_len
+// (<= K), after the select of a domain-mask class.
+void vamd_domain_count_add(
+    const int* log_nodes, const int* log_counts, const int* log_len,
+    const int* dom_of, int* dom_count, int D, int N, int K,
+    hipStream_t stream);
+
 // --- whole-cycle runner ----------------------------------------------------
 
 // One task class (a batch of identical pending tasks of one job).
@@ -202,5 +223,35 @@ void vamd_run_cycle_spread(
     const int32_t* spread_domains,      // HOST [G]: D of each group
     void* spread_scratch,               // device, 12*N bytes, 8-aligned
     hipStream_t stream);
+
+// vamd_run_cycle_spread plus a per-class mode column: 0 = topology spread
+// (as above), 1 = inter-pod affinity, 2 = keyed anti-affinity over the
+// class's group.  An affinity / anti class always runs vamd_score_cap ->
+// vamd_domain_mask -> vamd_select_commit (bulk by size, given
+// sort_scratch) -> vamd_domain_count_add: a launch count constant in
+// ntasks, never the fused, chain or megacycle path, and it reverts
+// through vamd_spread_revert.  With class_domain_mode == nullptr (or all
+// 0) this IS vamd_run_cycle_spread.
+void vamd_run_cycle_domains(
+    const VamdClassDesc* classes, int n_classes,
+    const VamdJobDesc* jobs, int n_jobs,
+    const float* alloc, float* used, const float* extra,
+    const uint8_t* ready, const int64_t* taints, const int64_t* planes,
+    const float* bias, const float* bias_rows,
+    const float* class_req, const int64_t* class_tol,
+    const int64_t* class_require, const int64_t* class_forbid,
+    const int32_t* class_min, const float* dim_w,
+    float* queue_alloc, const float* queue_limit,
+    float* score_scratch, int* cap_scratch,
+    int* log_nodes, int* log_counts, int* log_len,
+    int* class_placed, int* job_placed, uint8_t* job_flag,
+    unsigned* sort_scratch,
+    int N, int R, int W,
+    const int32_t* class_spread_group,  // HOST [C]: group index or -1
+    const int32_t* class_spread_skew,   // HOST [C]: maxSkew (mode 0)
+    const int32_t* class_domain_mode,   // HOST [C]: 0 / 1 / 2
+    const int32_t* spread_dom_of, int32_t* spread_count,
+    const int32_t* spread_count_off, const int32_t* spread_domains,
+    void* spread_scratch, hipStream_t stream);
 
 }  // extern "C"

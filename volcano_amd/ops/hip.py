@@ -59,6 +59,9 @@ def _load():
     lib.vamd_spread_select.restype = None
     lib.vamd_spread_revert.restype = None
     lib.vamd_run_cycle_spread.restype = None
+    lib.vamd_domain_mask.restype = None
+    lib.vamd_domain_count_add.restype = None
+    lib.vamd_run_cycle_domains.restype = None
     _lib = lib
     return lib
 
@@ -175,6 +178,46 @@ def spread_revert(flag, log_nodes, log_counts, log_len, req, used_t,
         c_int(N), c_int(R), _stream())
 
 
+def domain_mask(score, cap, dom_of, dom_count, mode, scratch=None):
+    """Inter-pod affinity (``mode`` 1) / keyed anti-affinity (``mode`` 2)
+    mask over ``score``/``cap`` (after score_cap, before select_commit),
+    from the group's live per-domain counts.  Both are changed in place."""
+    lib = _load()
+    N = score.shape[0]
+    D = dom_count.shape[0]
+    if not 1 <= D <= max(N, 1):
+        raise ValueError(f"domain_mask: D={D} outside [1, N={N}]")
+    if int(mode) not in (1, 2):
+        raise ValueError("domain_mask: mode must be 1 (affinity) or 2 (anti)")
+    if dom_of.shape[0] != N or cap.shape[0] != N:
+        raise ValueError("domain_mask: dom_of and cap must have one entry "
+                         "per node")
+    if scratch is None:
+        scratch = spread_scratch(N, score.device)
+    elif scratch.numel() * scratch.element_size() < 8 * D:
+        raise ValueError("domain_mask: scratch smaller than 8*D bytes")
+    lib.vamd_domain_mask(
+        _p(score), _p(cap), _p(dom_of), _p(dom_count), c_int(D),
+        c_int(int(mode)), _p(scratch), c_int(N), _stream())
+
+
+def domain_count_add(log_nodes, log_counts, log_len, dom_of, dom_count):
+    """The logged placements of a domain-mask class join the group's
+    per-domain counts (after select_commit)."""
+    lib = _load()
+    N = dom_of.shape[0]
+    D = dom_count.shape[0]
+    K = log_nodes.shape[0]
+    if not 1 <= D <= max(N, 1):
+        raise ValueError(f"domain_count_add: D={D} outside [1, N={N}]")
+    if log_counts.shape[0] != K:
+        raise ValueError("domain_count_add: log_nodes/log_counts differ in "
+                         "length")
+    lib.vamd_domain_count_add(
+        _p(log_nodes), _p(log_counts), _p(log_len), _p(dom_of),
+        _p(dom_count), c_int(D), c_int(N), c_int(K), _stream())
+
+
 def fused_score_select(alloc_t, used_t, extra_t, ready, taints, planes_t,
                        req, tolerated, require, forbid, w_least, w_most,
                        w_bal, dim_w, bias, score, cap, ntasks,
@@ -221,10 +264,34 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
     ``class_group``/``class_skew`` host int32 numpy [C], ``dom_of`` device
     i32 [G, N], ``count`` device i32 (groups back to back), ``count_off``/
     ``domains`` host int32 numpy [G], ``scratch`` device
-    (``spread_scratch``)."""
+    (``spread_scratch``).  An optional ``class_mode`` (host int32 numpy
+    [C]: 0 spread, 1 inter-pod affinity, 2 keyed anti-affinity) routes the
+    call through ``vamd_run_cycle_domains``."""
     lib = _load()
     R, N = alloc_t.shape
     W = planes_t.shape[0]
+    if spread is not None and spread.get("class_mode") is not None:
+        mode = spread["class_mode"]
+        if mode.shape[0] != n_classes or mode.dtype != "int32":
+            raise ValueError("run_cycle: class_mode must be int32 [C]")
+        lib.vamd_run_cycle_domains(
+            class_descs, c_int(n_classes),
+            job_descs, c_int(n_jobs),
+            _p(alloc_t), _p(used_t), _p(extra_t), _p(ready), _p(taints),
+            _p(planes_t), _p(bias), _p(bias_rows), _p(class_req),
+            _p(class_tol), _p(class_require), _p(class_forbid),
+            _p(class_min), _p(dim_w), _p(queue_alloc), _p(queue_limit),
+            _p(score_scratch), _p(cap_scratch), _p(log_nodes),
+            _p(log_counts), _p(log_len), _p(class_placed), _p(job_placed),
+            _p(job_flag), _p(sort_scratch), c_int(N), c_int(R), c_int(W),
+            c_void_p(spread["class_group"].ctypes.data),
+            c_void_p(spread["class_skew"].ctypes.data),
+            c_void_p(mode.ctypes.data),
+            _p(spread["dom_of"]), _p(spread["count"]),
+            c_void_p(spread["count_off"].ctypes.data),
+            c_void_p(spread["domains"].ctypes.data),
+            _p(spread["scratch"]), _stream())
+        return
     if spread is not None:
         lib.vamd_run_cycle_spread(
             class_descs, c_int(n_classes),

@@ -20,6 +20,8 @@ Kernel inventory (SURVEY.md §2.9 K1–K6 mapping):
 * ``cond_revert``    — K4 rollback of one class, gated on the job flag.
 * ``spread_select_commit`` / ``spread_revert`` — K2 select under a
   topology-spread bound checked before every placement, and its rollback.
+* ``affinity_select_commit`` — K2 select under an inter-pod (anti-)affinity
+  domain rule checked before every placement (reverts: ``spread_revert``).
 * ``drf_share``      — K3 dominant share per job.
 * ``waterfill``      — K3 proportion/capacity deserved water-filling.
 
@@ -297,6 +299,109 @@ def spread_revert(
         dom_count.index_add_(0, doms, -log_counts[:n])
     cond_revert(flag, log_nodes, log_counts, log_len, req, used,
                 queue_alloc, placed, job_placed)
+
+
+AFFINITY = 1                    # domain-rule modes of affinity_select_commit
+ANTI_AFFINITY = 2
+
+
+def affinity_select_commit(
+    score: torch.Tensor,        # [N] f32 from score_cap
+    cap: torch.Tensor,          # [N] i32
+    req: torch.Tensor,          # [R] f32
+    ntasks: int,
+    used: torch.Tensor,         # [N, R] f32 — updated in place (staged)
+    queue_alloc: torch.Tensor,  # [R] f32 in place
+    queue_limit: torch.Tensor,  # [R] f32
+    log_nodes: torch.Tensor,    # [K] i32 (K ≥ min(ntasks, N))
+    log_counts: torch.Tensor,   # [K] i32
+    log_len: torch.Tensor,      # [] i32
+    placed: torch.Tensor,       # [] i32
+    job_placed: torch.Tensor,   # [] i32
+    dom_of: torch.Tensor,       # [N] i32 node → domain (-1: unlabeled)
+    dom_count: torch.Tensor,    # [D] i32 group members per domain, in place
+    mode: int,                  # AFFINITY or ANTI_AFFINITY
+) -> None:
+    """Per-placement inter-pod (anti-)affinity fill for one task class (k8s
+    interpodaffinity filter, evaluated before EVERY instance).
+
+    A plain sequential loop on purpose — the source of truth for the HIP
+    composition ``domain_mask`` → ``select_commit`` → ``domain_count_add``.
+    Scores are static within the class; what moves is eligibility:
+
+    * ``AFFINITY``: while no domain holds a member, every feasible labelled
+      node is eligible and the first placement anchors its domain;
+      afterwards only nodes of domains with ``count > 0``.
+    * ``ANTI_AFFINITY``: only nodes of domains with ``count == 0``; a
+      placement closes its domain.
+
+    Unlabelled nodes (``dom_of < 0``) never take an instance.  Log, ``used``
+    and the counters follow ``spread_select_commit``.
+    """
+    if mode not in (AFFINITY, ANTI_AFFINITY):
+        raise ValueError("mode must be AFFINITY (1) or ANTI_AFFINITY (2)")
+    N = score.shape[0]
+    log_nodes.zero_()
+    log_counts.zero_()
+
+    headroom = queue_limit - queue_alloc
+    pos = req > EPS
+    per_dim = torch.where(pos, (headroom + EPS) / torch.clamp(req, min=EPS),
+                          torch.full_like(headroom, float(BIG_CAP)))
+    quota = int(per_dim.amin().clamp(min=0, max=float(BIG_CAP)).floor())
+    budget = min(int(ntasks), quota)
+
+    sc = score.tolist()
+    dom = dom_of.tolist()
+    cnt = dom_count.tolist()
+    rem = [int(c) if (s > NEG_INF and d >= 0) else 0
+           for s, c, d in zip(sc, cap.tolist(), dom)]
+    hosting = sum(1 for c in cnt if c > 0)
+    slot = {}                   # node → log entry
+    nodes: list = []
+    counts: list = []
+    total = 0
+    while total < budget:
+        best = -1
+        for n in range(N):
+            if rem[n] <= 0:
+                continue
+            c = cnt[dom[n]]
+            if mode == AFFINITY:
+                ok = hosting == 0 or c > 0
+            else:
+                ok = c == 0
+            if ok and (best < 0 or sc[n] > sc[best]):
+                best = n
+        if best < 0:
+            break
+        rem[best] -= 1
+        if cnt[dom[best]] == 0:
+            hosting += 1
+        cnt[dom[best]] += 1
+        total += 1
+        e = slot.get(best)
+        if e is None:
+            slot[best] = len(nodes)
+            nodes.append(best)
+            counts.append(1)
+        else:
+            counts[e] += 1
+
+    m = len(nodes)
+    assert m <= log_nodes.shape[0], "undo-log slot too small"
+    dev = score.device
+    idx = torch.tensor(nodes, dtype=torch.long, device=dev)
+    c32 = torch.tensor(counts, dtype=torch.int32, device=dev)
+    log_nodes[:m] = idx.to(torch.int32)
+    log_counts[:m] = c32
+    log_len.fill_(m)
+    dom_count.copy_(torch.tensor(cnt, dtype=torch.int32, device=dev))
+    used.index_add_(0, idx, c32.to(torch.float32).unsqueeze(1)
+                    * req.unsqueeze(0))
+    queue_alloc += torch.tensor(float(total), device=dev) * req
+    placed.fill_(total)
+    job_placed.add_(total)
 
 
 def drf_share(job_alloc: torch.Tensor, total: torch.Tensor) -> torch.Tensor:

@@ -255,14 +255,47 @@ class AllocateAction:
                 cp.forbid = cp.forbid.copy()
                 cp.forbid[bit // 64] &= ~(np.int64(1) << np.int64(bit % 64))
 
+        # exact inter-pod affinity (interpodaffinity plugin, ``exact:
+        # true``): the same routing for the classes of an affinity or keyed
+        # anti-affinity rule.  One domain rule per class — spread wins.
+        affinity_exact = getattr(ssn, "affinity_exact", None) \
+            if self.coordinator is None else None
+        affinity_group_of: Dict[int, int] = {}   # plugin rule → plan group
+
+        def affinity_attach(cp: ClassPlan, af) -> None:
+            """Route cp through the domain mask; its constraint words lose
+            the rule's session-open bit (hosting set / occupied domains) —
+            copy first, the memoized arrays are shared."""
+            g, mode = af
+            pg = affinity_group_of.get(g)
+            if pg is None:
+                pg = affinity_group_of[g] = plan.add_spread_group(
+                    affinity_exact.dom_of[g], affinity_exact.count[g])
+            cp.affinity = (pg, mode)
+            bit = affinity_exact.open_bit[g]
+            if bit is not None:
+                if mode == 1 and bit // 64 < len(cp.require):
+                    cp.require = cp.require.copy()
+                    cp.require[bit // 64] &= \
+                        ~(np.int64(1) << np.int64(bit % 64))
+                elif mode == 2 and bit // 64 < len(cp.forbid):
+                    cp.forbid = cp.forbid.copy()
+                    cp.forbid[bit // 64] &= \
+                        ~(np.int64(1) << np.int64(bit % 64))
+
         # such jobs never join a fused signature run
-        if spread_exact is not None and elig_l is not None:
+        if (spread_exact is not None or affinity_exact is not None) \
+                and elig_l is not None:
             for ix, jb in enumerate(jobs_l):
                 if elig_l[ix]:
                     t0_ = next(iter(jb.task_status_index.get(
                         _TS.PENDING, {}).values()), None)
-                    if t0_ is not None and \
-                            spread_exact.resolve_task(t0_) is not None:
+                    if t0_ is None:
+                        continue
+                    if (spread_exact is not None and
+                            spread_exact.resolve_task(t0_) is not None) or \
+                            (affinity_exact is not None and
+                             affinity_exact.resolve_task(t0_) is not None):
                         elig_l[ix] = False
 
         # nominated gangs take the host fast path — exclude them from runs
@@ -387,7 +420,10 @@ class AllocateAction:
                 # gangs back to back)
                 sp = spread_exact.resolve_task(first) \
                     if spread_exact is not None else None
-                if sp is None and not bias_fns and open_bundle is not None \
+                af = affinity_exact.resolve_task(first) \
+                    if affinity_exact is not None and sp is None else None
+                if sp is None and af is None and not bias_fns \
+                        and open_bundle is not None \
                         and open_key == (qi, sig):
                     tasks = list(pend.values())
                     mtm = job._mtm
@@ -441,8 +477,11 @@ class AllocateAction:
                     cp.bias = class_bias(tc, job)
                 if sp is not None:
                     spread_attach(cp, sp)
-                # biased and spread classes never fuse
-                if cp.bias is not None or cp.spread is not None:
+                elif af is not None:
+                    affinity_attach(cp, af)
+                # biased and domain-rule classes never fuse
+                if cp.bias is not None or cp.spread is not None \
+                        or cp.affinity is not None:
                     close_bundle()
                     plan.add_job(job, [cp])
                 else:
@@ -474,10 +513,14 @@ class AllocateAction:
                     w_most=w.get("most", 0.0), w_bal=w.get("bal", 0.0))
                 if bias_fns:
                     cp.bias = class_bias(tc, job)
-                if spread_exact is not None:
-                    sp = spread_exact.resolve_task(tc.tasks[0])
-                    if sp is not None:
-                        spread_attach(cp, sp)
+                sp = spread_exact.resolve_task(tc.tasks[0]) \
+                    if spread_exact is not None else None
+                if sp is not None:
+                    spread_attach(cp, sp)
+                elif affinity_exact is not None:
+                    af = affinity_exact.resolve_task(tc.tasks[0])
+                    if af is not None:
+                        affinity_attach(cp, af)
                 classes.append(cp)
             if skipped and classes and job.min_available > sum(
                     c.tclass.count for c in classes) + job.occupied_count:
@@ -489,7 +532,8 @@ class AllocateAction:
             bundleable = (len(classes) == 1 and job.occupied_count == 0
                           and classes[0].tclass.count == len(job.tasks)
                           and classes[0].bias is None
-                          and classes[0].spread is None)
+                          and classes[0].spread is None
+                          and classes[0].affinity is None)
             if bundleable:
                 cp = classes[0]
                 gang_min = max(job.min_available, cp.min_needed)

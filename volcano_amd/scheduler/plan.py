@@ -55,7 +55,8 @@ class BundleEntry:
 
 @dataclass(slots=True)
 class SpreadGroup:
-    """One topology-spread group of a cycle: the node → domain map and the
+    """One domain group of a cycle (topology spread, or inter-pod
+    (anti-)affinity over a topology key): the node → domain map and the
     group's member count per domain at cycle start.  The runners keep the
     live counts on the device for the whole cycle (every class of the
     group, in plan order, sees its predecessors' placements and reverts);
@@ -98,6 +99,11 @@ class ClassPlan:
     # placed by the per-placement topology-spread select instead of
     # select_commit.  Never combined with ``bundle``.
     spread: Optional[Tuple[int, int]] = None
+    # (index into CyclePlan.spread_groups, mode): inter-pod affinity
+    # (mode 1) or keyed anti-affinity (mode 2) enforced per placement over
+    # the group's domains — domain mask + select_commit + count update.
+    # Never combined with ``bundle`` or ``spread``.
+    affinity: Optional[Tuple[int, int]] = None
 
     @property
     def ntasks(self) -> int:
@@ -256,6 +262,19 @@ class CyclePlan:
                 if cp.bundle is not None:
                     raise ValueError(f"class {c}: spread classes never "
                                      "bundle")
+            if cp.affinity is not None:
+                g, mode = cp.affinity
+                if not 0 <= g < len(self.spread_groups):
+                    raise ValueError(f"class {c}: unknown affinity group {g}")
+                if mode not in (ref.AFFINITY, ref.ANTI_AFFINITY):
+                    raise ValueError(f"class {c}: affinity mode must be 1 "
+                                     "(affinity) or 2 (anti-affinity)")
+                if cp.bundle is not None:
+                    raise ValueError(f"class {c}: affinity classes never "
+                                     "bundle")
+                if cp.spread is not None:
+                    raise ValueError(f"class {c}: one domain rule per class "
+                                     "(spread and affinity both set)")
         self.log_total = off
         lens = np.fromiter((jp.class_end - jp.class_begin
                             for jp in self.jobs), dtype=np.int64,
@@ -301,8 +320,8 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
     plan.spread_counts = sp_cnt
 
     def revert(c, cp, flag, req, sl):
-        if cp.spread is not None:
-            g = cp.spread[0]
+        if cp.spread is not None or cp.affinity is not None:
+            g = (cp.spread or cp.affinity)[0]
             ref.spread_revert(flag, log_nodes[sl], log_counts[sl],
                               log_len[c], req, used,
                               plan.queue_alloc[cp.queue_idx],
@@ -339,6 +358,15 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
                     log_nodes[sl], log_counts[sl], log_len[c],
                     class_placed[c], job_placed[j],
                     sp_dom[g], sp_cnt[g], skew)
+            elif cp.affinity is not None:
+                g, mode = cp.affinity
+                ref.affinity_select_commit(
+                    score, cap, req, cp.ntasks, used,
+                    plan.queue_alloc[cp.queue_idx],
+                    plan.queue_limit[cp.queue_idx],
+                    log_nodes[sl], log_counts[sl], log_len[c],
+                    class_placed[c], job_placed[j],
+                    sp_dom[g], sp_cnt[g], mode)
             else:
                 ref.select_commit(score, cap, req, cp.ntasks, used,
                                   plan.queue_alloc[cp.queue_idx],
@@ -452,16 +480,23 @@ def run_plan_hip(plan: CyclePlan) -> CycleResult:
     sort_scratch = torch.empty(4 * N, dtype=torch.int32, device=dev) \
         if C and int(cds["ntasks"].max()) >= 512 and N >= 512 else None
 
-    # topology-spread classes: group tables go to the device once, the
-    # per-class (group, maxSkew) columns stay host-side for the runner
+    # domain-rule classes (topology spread, inter-pod affinity): group
+    # tables go to the device once, the per-class (group, maxSkew, mode)
+    # columns stay host-side for the runner.  The mode column exists only
+    # when the plan has affinity classes — otherwise the call is the one a
+    # spread-only plan always made.
     spread = None
-    if any(cp.spread is not None for cp in plan.classes):
+    any_aff = any(cp.affinity is not None for cp in plan.classes)
+    if any_aff or any(cp.spread is not None for cp in plan.classes):
         groups = plan.spread_groups
         cg = np.full(C, -1, dtype=np.int32)
         cs = np.ones(C, dtype=np.int32)
+        cm = np.zeros(C, dtype=np.int32)
         for c, cp in enumerate(plan.classes):
             if cp.spread is not None:
                 cg[c], cs[c] = cp.spread
+            elif cp.affinity is not None:
+                cg[c], cm[c] = cp.affinity
         doms = np.array([g.count.shape[0] for g in groups], dtype=np.int32)
         offs = (np.cumsum(doms) - doms).astype(np.int32)
         count = torch.from_numpy(
@@ -474,6 +509,8 @@ def run_plan_hip(plan: CyclePlan) -> CycleResult:
             ).to(dev).contiguous(),
             count=count, count_off=offs, domains=doms,
             scratch=hip.spread_scratch(N, dev))
+        if any_aff:
+            spread["class_mode"] = cm
         plan.spread_counts = [count[int(o):int(o) + int(d)]
                               for o, d in zip(offs, doms)]
 
