@@ -27,7 +27,7 @@ SOURCES = ["scheduler_kernels.hip", "cycle_runner.hip"]
 HOST_LIB_PATH = PKG_DIR / ("_vamd_host" + (
     sysconfig.get_config_var("EXT_SUFFIX") or ".so"))
 HOST_SOURCES = ["vamd_host.cpp"]
-HOST_DEPS = HOST_SOURCES + ["settle_core.h"]
+HOST_DEPS = HOST_SOURCES + ["settle_core.h", "lookahead.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("VAMD_GPU_ARCH", "gfx950")
 

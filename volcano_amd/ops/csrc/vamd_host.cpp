@@ -11,6 +11,10 @@
 // (bundle_entries) and the bulk pod-group phase store
 // (set_podgroup_phase).  Each has its Python loop as oracle and fallback.
 //
+// All five loops are chains of dependent loads through cold objects; they
+// run in blocks with a prefetching lookahead in front of each block
+// (lookahead.h states the technique and its safety invariant).
+//
 // Host-only C++ (no HIP); not linked against libpython.
 #define PY_SSIZE_T_CLEAN
 #include <Python.h>
@@ -20,9 +24,12 @@
 #include <cstring>
 #include <vector>
 
+#include "lookahead.h"
 #include "settle_core.h"
 
 namespace {
+
+namespace la = vamd::la;
 
 struct Ref {                       // owning reference, released on scope exit
     PyObject* p;
@@ -78,6 +85,34 @@ PyObject *s_bundle, *s_log_off, *s_job_key, *s_tclass, *s_tasks, *s_ntasks,
     *s_min_needed, *s_job, *s_key, *s_name, *s_batches, *s_node_name,
     *s_status, *s_f, *s_r, *s_task_status_index, *s_occ, *s_alloc_vec,
     *s_podgroup, *s_phase, *s_tver, *s_gated, *s_job_gated, *s_values;
+
+struct TaskStore;
+
+// Block lookaheads of the five loops, defined below the attribute caches
+// they read.  Each obeys the invariant of lookahead.h: no stores, no
+// reference counts, no Python code, nothing kept past its return.
+void la_scan_block(PyObject* jobs, Py_ssize_t k0, Py_ssize_t n,
+                   PyObject* pending, Py_hash_t h_pending, PyObject* failed,
+                   Py_hash_t h_failed);
+void la_phase_block(PyObject* jobs, Py_ssize_t k0, Py_ssize_t n);
+void la_bundle_block(PyObject* jobs_l, Py_ssize_t k0, Py_ssize_t n,
+                     PyObject* pending, Py_hash_t h_pending);
+void la_finish_block(PyObject* by_job, Py_ssize_t pos, Py_ssize_t n,
+                     PyObject* jobs, PyObject* pending, Py_hash_t h_pending,
+                     PyObject* bound, Py_hash_t h_bound);
+void la_entries(PyObject* bundle, Py_ssize_t b0, Py_ssize_t n);
+void la_commit_block(PyObject* bundle, Py_ssize_t b0, Py_ssize_t n,
+                     const vamd::SettleOut& so, size_t pp, PyObject* nodes,
+                     const TaskStore& ts);
+
+// Hash of a non-str dict key (a status enum: hashing one runs Python
+// code), taken once per call before the first block; -1 turns the hops
+// through that key off.
+Py_hash_t la_key_hash(PyObject* key) {
+    const Py_hash_t h = PyObject_Hash(key);
+    if (h == -1) PyErr_Clear();
+    return h;
+}
 
 // Offset of a plain object-valued __slots__ member of `tp`, or -1 when
 // `name` is anything else (property, instance-dict attribute, read-only
@@ -344,6 +379,7 @@ PyObject* apply_walk(PyObject*, PyObject* args) {
     const int32_t* lc_p = static_cast<const int32_t*>(lc.v.buf);
     const int32_t* ll_p = static_cast<const int32_t*>(ll.v.buf);
     const Py_ssize_t n_jobs = jf.count();
+    const la::Config pfc = la::config();
 
     GcPause gc_pause;
     Walk w;
@@ -439,7 +475,14 @@ PyObject* apply_walk(PyObject*, PyObject* args) {
 
         e_ntasks.resize(static_cast<size_t>(n_entries));
         e_min.resize(static_cast<size_t>(n_entries));
+        const bool ahead = pfc.on && n_entries >= la::kMinWindow;
         for (Py_ssize_t b = 0; b < n_entries; ++b) {
+            // one hop only (the sizes are small cached ints), so this
+            // pass fetches the block AFTER the one it is about to read
+            if (ahead && b % pfc.block == 0) {
+                if (b == 0) la_entries(bundle.p, 0, pfc.block);
+                la_entries(bundle.p, b + pfc.block, pfc.block);
+            }
             PyObject* be = PyList_GET_ITEM(bundle.p, b);
             long nt, mn;
             if (!attr_long(be, s_ntasks, &nt) ||
@@ -459,6 +502,9 @@ PyObject* apply_walk(PyObject*, PyObject* args) {
             return nullptr;
         size_t pp = 0;
         for (Py_ssize_t b = 0; b < n_entries; ++b) {
+            if (ahead && b % pfc.block == 0)
+                la_commit_block(bundle.p, b, pfc.block, so, pp, nodes,
+                                w.tstore);
             const uint8_t oc = so.outcome[b];
             if (oc == vamd::SETTLE_GANG_MISS) { ++w.n_missed; continue; }
             if (oc == vamd::SETTLE_LOST) { ++w.n_lost; continue; }
@@ -510,9 +556,18 @@ PyObject* finish_binds(PyObject*, PyObject* args) {
                           &pending, &bound))
         return nullptr;
     GcPause gc_pause;                  // one fresh bucket dict per job
-    Py_ssize_t pos = 0;
+    const la::Config pfc = la::config();
+    const bool ahead = pfc.on && PyDict_GET_SIZE(by_job) >= la::kMinWindow;
+    const Py_hash_t h_pending = ahead ? la_key_hash(pending) : -1;
+    const Py_hash_t h_bound = ahead ? la_key_hash(bound) : -1;
+    Py_ssize_t pos = 0, seen = 0;
     PyObject *key, *ts;
-    while (PyDict_Next(by_job, &pos, &key, &ts)) {
+    for (;;) {
+        if (ahead && seen % pfc.block == 0)
+            la_finish_block(by_job, pos, pfc.block, jobs, pending, h_pending,
+                            bound, h_bound);
+        if (!PyDict_Next(by_job, &pos, &key, &ts)) break;
+        ++seen;
         Ref job(map_get(jobs, key));
         if (!job) {
             if (PyErr_Occurred()) return nullptr;
@@ -622,11 +677,23 @@ struct SlotAttr {
         Py_XDECREF(old);
         return true;
     }
+    // Lookahead only: the borrowed value without the attribute protocol —
+    // the slot when it is already resolved for o's type (never resolved
+    // here: that runs Python code), else the entry of o's instance dict
+    // `d` — or nullptr.
+    PyObject* peek(PyObject* o, PyObject* d) const {
+        if (o == nullptr) return nullptr;
+        if (type != nullptr && Py_TYPE(o) == type && off >= 0)
+            return *reinterpret_cast<PyObject**>(
+                reinterpret_cast<char*>(o) + off);
+        return la::dict_value(d, *name, la::str_hash(*name));
+    }
 };
 
 SlotAttr a_job_idx(&s_task_status_index), a_job_occ(&s_occ),
     a_job_pg(&s_podgroup), a_job_tver(&s_tver), a_job_key(&s_key),
-    a_pg_status(&s_status), a_st_phase(&s_phase), a_task_gated(&s_gated);
+    a_pg_status(&s_status), a_st_phase(&s_phase), a_task_gated(&s_gated),
+    a_node_name(&s_name), a_node_batches(&s_batches);   // peeked only
 
 // getattr(o, name, <absent>): 1 found (new reference in *out), 0 absent,
 // -1 error.
@@ -696,11 +763,18 @@ PyObject* scan_jobs(PyObject*, PyObject* args) {
 
     Ref dirty(PyList_New(0));
     if (!dirty) return nullptr;
+    const la::Config pfc = la::config();
+    const bool ahead = pfc.on && J >= la::kMinWindow;
+    const Py_hash_t h_pending = ahead ? la_key_hash(pending) : -1;
+    const Py_hash_t h_failed = ahead ? la_key_hash(failed) : -1;
     for (Py_ssize_t k = 0; k < J; ++k) {
         if (PyList_GET_SIZE(jobs) != J) {   // an attribute hook resized it
             PyErr_SetString(PyExc_RuntimeError, "job list changed size");
             return nullptr;
         }
+        if (ahead && k % pfc.block == 0)
+            la_scan_block(jobs, k, pfc.block, pending, h_pending, failed,
+                          h_failed);
         Ref job(PyList_GET_ITEM(jobs, k));
         Py_INCREF(job.p);
         Ref v(a_job_occ.get(job.p));
@@ -791,6 +865,234 @@ struct EntryType {
 
 EntryType entry_type;
 
+// ---- block lookaheads ------------------------------------------------------
+// Every pass below takes one hop for all elements of the block and
+// prefetches what the next pass dereferences; nullptr drops an element.
+
+// Elements [k0, k0 + n) of an exact list, clamped to its current size;
+// prefetches their headers and returns the count.
+Py_ssize_t la_load(PyObject* list, Py_ssize_t k0, Py_ssize_t n,
+                   PyObject** out) {
+    const Py_ssize_t size = PyList_GET_SIZE(list);
+    if (n > la::kMaxBlock) n = la::kMaxBlock;
+    if (k0 < 0 || k0 >= size) return 0;
+    if (k0 + n > size) n = size - k0;
+    for (Py_ssize_t e = 0; e < n; ++e) {
+        out[e] = PyList_GET_ITEM(list, k0 + e);
+        la::pf_obj(out[e]);
+    }
+    return n;
+}
+
+// Instance dicts of obj[0..n): two passes (dict object, then its storage).
+void la_dicts(PyObject* const* obj, Py_ssize_t n, PyObject** d) {
+    for (Py_ssize_t e = 0; e < n; ++e) d[e] = la::inst_dict(obj[e]);
+    for (Py_ssize_t e = 0; e < n; ++e) d[e] = la::dict_storage(d[e]);
+}
+
+// One attribute hop: obj[e] (header in cache) -> out[e], header
+// prefetched.  `out` may be `obj`.
+void la_hop(PyObject* const* obj, Py_ssize_t n, const SlotAttr& a,
+            PyObject** out) {
+    PyObject* d[la::kMaxBlock];
+    la_dicts(obj, n, d);
+    for (Py_ssize_t e = 0; e < n; ++e) {
+        out[e] = a.peek(obj[e], d[e]);
+        la::pf_obj(out[e]);
+    }
+}
+
+void la_phase_block(PyObject* jobs, Py_ssize_t k0, Py_ssize_t n) {
+    PyObject* o[la::kMaxBlock];
+    n = la_load(jobs, k0, n, o);
+    la_hop(o, n, a_job_pg, o);         // job -> podgroup
+    la_hop(o, n, a_pg_status, o);      // -> status
+    la_hop(o, n, a_st_phase, o);       // -> phase
+}
+
+void la_scan_block(PyObject* jobs, Py_ssize_t k0, Py_ssize_t n,
+                   PyObject* pending, Py_hash_t h_pending, PyObject* failed,
+                   Py_hash_t h_failed) {
+    PyObject *job[la::kMaxBlock], *d[la::kMaxBlock], *idx[la::kMaxBlock],
+        *pg[la::kMaxBlock];
+    n = la_load(jobs, k0, n, job);
+    la_dicts(job, n, d);
+    for (Py_ssize_t e = 0; e < n; ++e) {
+        idx[e] = a_job_idx.peek(job[e], d[e]);
+        la::pf_dict(idx[e]);
+        pg[e] = a_job_pg.peek(job[e], d[e]);
+        la::pf_obj(pg[e]);
+        la::pf(a_job_occ.peek(job[e], d[e]));
+        la::pf(a_job_tver.peek(job[e], d[e]));
+    }
+    for (Py_ssize_t e = 0; e < n; ++e) idx[e] = la::dict_storage(idx[e]);
+    for (Py_ssize_t e = 0; e < n; ++e) {   // bucket lengths only
+        la::pf_dict(la::dict_value(idx[e], pending, h_pending));
+        la::pf_dict(la::dict_value(idx[e], failed, h_failed));
+    }
+    la_hop(pg, n, a_pg_status, pg);
+    la_hop(pg, n, a_st_phase, pg);
+}
+
+void la_bundle_block(PyObject* jobs_l, Py_ssize_t k0, Py_ssize_t n,
+                     PyObject* pending, Py_hash_t h_pending) {
+    PyObject *job[la::kMaxBlock], *d[la::kMaxBlock], *b[la::kMaxBlock];
+    n = la_load(jobs_l, k0, n, job);
+    la_dicts(job, n, d);
+    for (Py_ssize_t e = 0; e < n; ++e) {
+        b[e] = a_job_idx.peek(job[e], d[e]);
+        la::pf_dict(b[e]);
+        la::pf(a_job_key.peek(job[e], d[e]));
+    }
+    for (Py_ssize_t e = 0; e < n; ++e) b[e] = la::dict_storage(b[e]);
+    for (Py_ssize_t e = 0; e < n; ++e) {   // index -> pending bucket
+        b[e] = la::dict_value(b[e], pending, h_pending);
+        la::pf_dict(b[e]);
+    }
+    for (Py_ssize_t e = 0; e < n; ++e) b[e] = la::dict_storage(b[e]);
+    // the tasks get an incref (first line); the head's `gated` slot is
+    // read.  Its address is only prefetched, so the task's type, not yet
+    // in cache, need not be checked.
+    const Py_ssize_t g_off =
+        a_task_gated.type != nullptr ? a_task_gated.off : -1;
+    for (Py_ssize_t e = 0; e < n; ++e) {
+        if (b[e] == nullptr) continue;
+        Py_ssize_t pos = 0, cnt = 0;
+        PyObject* t;
+        while (cnt < la::kMaxTasks && PyDict_Next(b[e], &pos, nullptr, &t)) {
+            la::pf(t);
+            if (cnt == 0 && g_off >= 0)
+                la::pf(reinterpret_cast<char*>(t) + g_off);
+            ++cnt;
+        }
+    }
+}
+
+void la_finish_block(PyObject* by_job, Py_ssize_t pos, Py_ssize_t n,
+                     PyObject* jobs, PyObject* pending, Py_hash_t h_pending,
+                     PyObject* bound, Py_hash_t h_bound) {
+    PyObject *key[la::kMaxBlock], *job[la::kMaxBlock], *d[la::kMaxBlock],
+        *idx[la::kMaxBlock];
+    Py_hash_t h[la::kMaxBlock];
+    if (n > la::kMaxBlock) n = la::kMaxBlock;
+    Py_ssize_t m = 0;
+    PyObject *k, *ts;
+    while (m < n && PyDict_Next(by_job, &pos, &k, &ts)) {
+        key[m++] = k;
+        la::pf_obj(k);                 // its cached hash
+        la::pf_list(ts);               // its length
+    }
+    n = m;
+    // the job table is large: index slot, entry, then the job itself
+    const bool probe = PyDict_CheckExact(jobs);
+    for (Py_ssize_t e = 0; e < n; ++e) {
+        h[e] = probe ? la::str_hash(key[e]) : -1;
+        if (h[e] != -1) la::dict_pf_index(jobs, h[e]);
+    }
+    for (Py_ssize_t e = 0; e < n; ++e)
+        if (h[e] != -1) la::dict_pf_entry(jobs, h[e]);
+    for (Py_ssize_t e = 0; e < n; ++e) {
+        job[e] = h[e] != -1 ? la::dict_value(jobs, key[e], h[e]) : nullptr;
+        la::pf_obj(job[e]);
+    }
+    la_dicts(job, n, d);
+    for (Py_ssize_t e = 0; e < n; ++e) {   // `_alloc_vec` shares the storage
+        idx[e] = a_job_idx.peek(job[e], d[e]);
+        la::pf_dict(idx[e]);
+        la::pf(a_job_occ.peek(job[e], d[e]));
+    }
+    for (Py_ssize_t e = 0; e < n; ++e) idx[e] = la::dict_storage(idx[e]);
+    for (Py_ssize_t e = 0; e < n; ++e) {
+        la::pf_dict(la::dict_value(idx[e], pending, h_pending));
+        la::pf_dict(la::dict_value(idx[e], bound, h_bound));
+    }
+}
+
+// Bundle entries [b0, b0 + n): their slots (one or two lines each).
+void la_entries(PyObject* bundle, Py_ssize_t b0, Py_ssize_t n) {
+    const Py_ssize_t size = PyList_GET_SIZE(bundle);
+    if (b0 < 0 || b0 >= size) return;
+    if (b0 + n > size) n = size - b0;
+    for (Py_ssize_t e = 0; e < n; ++e)
+        la::pf_span(PyList_GET_ITEM(bundle, b0 + e), 56, 2);
+}
+
+// The commits of entries [b0, b0 + n): entry -> job (-> key), job_key,
+// tasks list -> items -> the task lines the walk writes; and for the
+// pieces of the block, node -> name, _batches -> its tail.
+void la_commit_block(PyObject* bundle, Py_ssize_t b0, Py_ssize_t n,
+                     const vamd::SettleOut& so, size_t pp, PyObject* nodes,
+                     const TaskStore& ts) {
+    PyObject *be[la::kMaxBlock], *job[la::kMaxBlock], *tl[la::kMaxBlock],
+        *d[la::kMaxBlock];
+    const Py_ssize_t size = PyList_GET_SIZE(bundle);
+    if (n > la::kMaxBlock) n = la::kMaxBlock;
+    if (b0 < 0 || b0 >= size) return;
+    if (b0 + n > size) n = size - b0;
+    Py_ssize_t m = 0;
+    for (Py_ssize_t b = b0; b < b0 + n; ++b) {
+        if (so.outcome[b] != vamd::SETTLE_COMMITTED) continue;
+        be[m] = PyList_GET_ITEM(bundle, b);
+        la::pf_span(be[m], 56, 2);
+        ++m;
+    }
+    // nodes of the block's pieces (a run on one node counts once)
+    PyObject* nd[la::kMaxBlock];
+    Py_ssize_t nn = 0;
+    const Py_ssize_t n_nodes = PyList_GET_SIZE(nodes);
+    int32_t last = -1;
+    for (size_t p = pp; p < so.n_pieces && so.p_entry[p] < b0 + n &&
+                        nn < la::kMaxBlock; ++p) {
+        const int32_t nid = so.p_node[p];
+        if (nid == last || nid < 0 || nid >= n_nodes) continue;
+        last = nid;
+        nd[nn] = PyList_GET_ITEM(nodes, nid);
+        la::pf_obj(nd[nn]);
+        ++nn;
+    }
+    bool slots = entry_type.type != nullptr;
+    for (int i = 0; i < 5; ++i) slots = slots && entry_type.off[i] >= 0;
+    for (Py_ssize_t e = 0; e < m; ++e) {
+        job[e] = tl[e] = nullptr;
+        if (!slots || Py_TYPE(be[e]) != entry_type.type) continue;
+        char* base = reinterpret_cast<char*>(be[e]);
+        la::pf(*reinterpret_cast<PyObject**>(base + entry_type.off[0]));
+        tl[e] = *reinterpret_cast<PyObject**>(base + entry_type.off[1]);
+        job[e] = *reinterpret_cast<PyObject**>(base + entry_type.off[4]);
+        la::pf_list(tl[e]);
+        la::pf_obj(job[e]);
+    }
+    for (Py_ssize_t e = 0; e < m; ++e) {
+        tl[e] = la::list_items(tl[e]);
+        d[e] = la::inst_dict(job[e]);
+    }
+    const bool tslots = ts.type && ts.off_node >= 0 && ts.off_status >= 0;
+    for (Py_ssize_t e = 0; e < m; ++e) {
+        d[e] = la::dict_storage(d[e]);
+        if (tl[e] == nullptr) continue;
+        Py_ssize_t k = PyList_GET_SIZE(tl[e]);
+        if (k > la::kMaxTasks) k = la::kMaxTasks;
+        for (Py_ssize_t i = 0; i < k; ++i) {
+            char* t = reinterpret_cast<char*>(PyList_GET_ITEM(tl[e], i));
+            la::pf(t);
+            if (tslots) {              // addresses only, type unchecked
+                la::pf(t + ts.off_node);
+                la::pf(t + ts.off_status);
+            }
+        }
+    }
+    for (Py_ssize_t e = 0; e < m; ++e) la::pf(a_job_key.peek(job[e], d[e]));
+
+    PyObject* bt[la::kMaxBlock];
+    la_dicts(nd, nn, d);
+    for (Py_ssize_t e = 0; e < nn; ++e) {
+        la::pf(a_node_name.peek(nd[e], d[e]));
+        bt[e] = a_node_batches.peek(nd[e], d[e]);
+        la::pf_list(bt[e]);
+    }
+    for (Py_ssize_t e = 0; e < nn; ++e) la::pf_list_tail(bt[e]);
+}
+
 // The values of a pending bucket as a fresh list, or nullptr with *skip
 // set when the job has nothing to plan (empty bucket, or a gated head).
 PyObject* pending_tasks(PyObject* pend, bool* skip) {
@@ -852,10 +1154,18 @@ PyObject* bundle_entries(PyObject*, PyObject* args) {
     Ref entries(PyList_New(0));
     if (!entries) return nullptr;
     long long total = 0, mn = 1LL << 60;
+    // short runs (the mixed workload makes thousands) go without
+    const la::Config pfc = la::config();
+    const bool ahead = pfc.on && j - i >= la::kMinWindow;
+    const Py_hash_t h_pending = ahead ? la_key_hash(pending) : -1;
     for (Py_ssize_t k = i; k < j; ++k) {
         if (k >= PyList_GET_SIZE(jobs_l) || k >= PyList_GET_SIZE(gm_l)) {
             PyErr_SetString(PyExc_RuntimeError, "worksheet changed size");
             return nullptr;
+        }
+        if (ahead && (k - i) % pfc.block == 0) {
+            const Py_ssize_t n = j - k < pfc.block ? j - k : pfc.block;
+            la_bundle_block(jobs_l, k, n, pending, h_pending);
         }
         Ref jb(PyList_GET_ITEM(jobs_l, k));
         Py_INCREF(jb.p);
@@ -901,7 +1211,11 @@ PyObject* set_podgroup_phase(PyObject*, PyObject* args) {
         return nullptr;
     Ref changed(PyList_New(0)), gated(PyList_New(0));
     if (!changed || !gated) return nullptr;
+    const la::Config pfc = la::config();
+    const bool ahead = pfc.on && PyList_GET_SIZE(jobs) >= la::kMinWindow;
     for (Py_ssize_t k = 0; k < PyList_GET_SIZE(jobs); ++k) {
+        if (ahead && k % pfc.block == 0)
+            la_phase_block(jobs, k, pfc.block);
         Ref job(PyList_GET_ITEM(jobs, k));
         Py_INCREF(job.p);
         Ref pg(a_job_pg.get(job.p));
@@ -977,7 +1291,15 @@ PyMODINIT_FUNC PyInit__vamd_host(void) {
         {&s_job_gated, "_gated"}, {&s_values, "values"}};
     for (auto& nm : names) {
         *nm.slot = PyUnicode_InternFromString(nm.text);
-        if (*nm.slot == nullptr) return nullptr;
+        // the lookahead reads the cached hash of these names
+        if (*nm.slot == nullptr || PyObject_Hash(*nm.slot) == -1)
+            return nullptr;
     }
-    return PyModule_Create(&moddef);
+    PyObject* m = PyModule_Create(&moddef);
+    if (m != nullptr &&
+        PyModule_AddIntConstant(m, "PREFETCH_BLOCK", la::kDefaultBlock) != 0) {
+        Py_DECREF(m);
+        return nullptr;
+    }
+    return m;
 }

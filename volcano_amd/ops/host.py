@@ -14,6 +14,11 @@ The other per-job loops of a cycle (JobTable column scan, fused-run
 bundle entries, bulk pod-group phase stores) follow the same scheme under
 their own switch, ``VAMD_NATIVE_JOBS=0``; ``native_jobs_enabled()`` is the
 per-cycle test and is also false for a stale module without them.
+
+All the native loops run in blocks behind a prefetching lookahead
+(``csrc/lookahead.h``).  ``VAMD_HOST_PREFETCH=0`` turns it off; the
+extension reads it from the process environment at every call, so
+``os.environ`` changes take effect at once.  Results do not depend on it.
 """
 
 from __future__ import annotations
