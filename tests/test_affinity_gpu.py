@@ -1,7 +1,8 @@
 """``domain_mask`` → ``select_commit`` → ``domain_count_add`` and the routing
-of ``vamd_run_cycle_domains`` against the oracle: logs entry for entry and in
-order, per-domain counts, usage, queue allocation and the counters, bit for
-bit.  Inputs are exact in f32 (``_affinity_cases``)."""
+of ``vamd_run_cycle`` by its ``class_mode`` column against the oracle: logs
+entry for entry and in order, per-domain counts, usage, queue allocation
+and the counters, bit for bit.  Inputs are exact in f32
+(``_affinity_cases``)."""
 
 import functools
 
@@ -294,7 +295,7 @@ def test_plan_without_domain_classes_takes_the_old_entry_point(N):
     case, want, _ = plan_oracle(N, rules=False)
     calls = []
     got = run_plan(case, rules=False, calls=calls)
-    assert calls == [None]                  # vamd_run_cycle
+    assert calls == [None]                  # no domain block at all
     ac.compare_plans(want, got)
 
 

@@ -1,4 +1,4 @@
-"""``vamd_spread_select`` and the spread routing of ``vamd_run_cycle_spread``
+"""``vamd_spread_select`` and the spread routing of ``vamd_run_cycle``
 against the oracle: logs entry for entry and in order, per-domain counts,
 usage, queue allocation and the counters, bit for bit.
 

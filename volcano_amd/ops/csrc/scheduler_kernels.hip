@@ -190,6 +190,53 @@ DEVINL ValIdx wave_reduce(ValIdx x) {
     return x;
 }
 
+// queue quota -> instance budget of one class (proportion/capacity
+// Allocatable check, session_plugins.go:405 — enforced exactly, on device).
+// Serial over R: one thread calls it and publishes the result.
+DEVINL long long dev_queue_budget(
+    const float* __restrict__ req, const float* __restrict__ queue_limit,
+    const float* __restrict__ queue_alloc, int ntasks, int R)
+{
+    long long quota = BIG_CAP;
+    for (int r = 0; r < R; ++r) {
+        float rq = req[r];
+        if (rq > EPS) {
+            float head = queue_limit[r] - queue_alloc[r];
+            float qq = (head + EPS) / rq;
+            if (qq > (float)BIG_CAP) qq = (float)BIG_CAP;
+            long long q = (long long)floorf(qq);
+            quota = min(quota, max(q, 0ll));
+        }
+    }
+    return min((long long)ntasks, quota);
+}
+
+// Commit epilogue of the log-first selects (bulk, spread), whole 1024-
+// thread block: ONE (float)count * req per log entry goes into `used`
+// (a wave per entry), the class total into queue_alloc, then the counters
+// are published.
+DEVINL void dev_commit_log(
+    const int* __restrict__ log_nodes, const int* __restrict__ log_counts,
+    int len, int total, const float* __restrict__ req,
+    float* __restrict__ used, float* __restrict__ queue_alloc,
+    int* __restrict__ log_len, int* __restrict__ placed,
+    int* __restrict__ job_placed, int N, int R)
+{
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    for (int e = tid / WAVE; e < len; e += 1024 / WAVE) {
+        int node = log_nodes[e];
+        int cnt = log_counts[e];
+        if (lane < R) used[(size_t)lane * N + node] += (float)cnt * req[lane];
+    }
+    if (tid < R) queue_alloc[tid] += (float)total * req[tid];
+    if (tid == 0) {
+        *log_len = len;
+        *placed = total;
+        *job_placed += total;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // K2 select + K4 gang-transactional placement for one task class.
 //   ONE workgroup (1024 threads = 16 waves).  Iterative argmax over the
@@ -231,20 +278,7 @@ __device__ void dev_select_commit(
     const int wid = tid / WAVE;
 
     if (tid == 0) {
-        // queue quota -> instance budget (proportion/capacity Allocatable
-        // check, session_plugins.go:405 — enforced exactly, on device)
-        long long quota = BIG_CAP;
-        for (int r = 0; r < R; ++r) {
-            float rq = req[r];
-            if (rq > EPS) {
-                float head = queue_limit[r] - queue_alloc[r];
-                float qq = (head + EPS) / rq;
-                if (qq > (float)BIG_CAP) qq = (float)BIG_CAP;
-                long long q = (long long)floorf(qq);
-                quota = min(quota, max(q, 0ll));
-            }
-        }
-        s_budget = min((long long)ntasks, quota);
+        s_budget = dev_queue_budget(req, queue_limit, queue_alloc, ntasks, R);
         s_remaining = (int)min(s_budget, (long long)INT32_MAX);
         s_cursor = 0;
     }
@@ -519,18 +553,7 @@ bulk_select_kernel(
     unsigned* ids_b = scratch + 3 * (size_t)N;
 
     if (tid == 0) {
-        long long quota = BIG_CAP;
-        for (int r = 0; r < R; ++r) {
-            float rq = req[r];
-            if (rq > EPS) {
-                float head = queue_limit[r] - queue_alloc[r];
-                float qq = (head + EPS) / rq;
-                if (qq > (float)BIG_CAP) qq = (float)BIG_CAP;
-                long long q = (long long)floorf(qq);
-                quota = min(quota, max(q, 0ll));
-            }
-        }
-        s_budget = min((long long)ntasks, quota);
+        s_budget = dev_queue_budget(req, queue_limit, queue_alloc, ntasks, R);
         s_carry_cap = 0;
         s_carry_log = 0;
     }
@@ -687,17 +710,8 @@ bulk_select_kernel(
         return;
     }
     // commit: apply the logged takes to the staged usage
-    for (int e = wid; e < m; e += BS_WAVES) {
-        int node = log_nodes[e];
-        int cnt = log_counts[e];
-        if (lane < R) used[(size_t)lane * N + node] += (float)cnt * req[lane];
-    }
-    if (tid < R) queue_alloc[tid] += (float)total * req[tid];
-    if (tid == 0) {
-        *log_len = m;
-        *placed = total;
-        *job_placed += total;
-    }
+    dev_commit_log(log_nodes, log_counts, m, total, req, used, queue_alloc,
+                   log_len, placed, job_placed, N, R);
 }
 
 // ---------------------------------------------------------------------------
@@ -796,18 +810,8 @@ spread_select_kernel(
     const int wid = tid / WAVE;
 
     if (tid == 0) {
-        long long quota = BIG_CAP;
-        for (int r = 0; r < R; ++r) {
-            float rq = req[r];
-            if (rq > EPS) {
-                float hd = queue_limit[r] - queue_alloc[r];
-                float qq = (hd + EPS) / rq;
-                if (qq > (float)BIG_CAP) qq = (float)BIG_CAP;
-                long long q = (long long)floorf(qq);
-                quota = min(quota, max(q, 0ll));
-            }
-        }
-        long long b = min((long long)ntasks, quota);
+        long long b = dev_queue_budget(req, queue_limit, queue_alloc, ntasks,
+                                       R);
         s_budget = (D > 0 && b > 0) ? (int)b : 0;
         s_cursor = 0;
         s_total = 0;
@@ -940,18 +944,8 @@ spread_select_kernel(
         }
         if (tid == 0) { *log_len = cursor; *placed = 0; }
     } else {
-        for (int e = wid; e < cursor; e += SP_WAVES) {
-            int node = log_nodes[e];
-            int cnt = log_counts[e];
-            if (lane < R)
-                used[(size_t)lane * N + node] += (float)cnt * req[lane];
-        }
-        if (tid < R) queue_alloc[tid] += (float)total * req[tid];
-        if (tid == 0) {
-            *log_len = cursor;
-            *placed = total;
-            *job_placed += total;
-        }
+        dev_commit_log(log_nodes, log_counts, cursor, total, req, used,
+                       queue_alloc, log_len, placed, job_placed, N, R);
     }
 }
 
@@ -1159,24 +1153,18 @@ megacycle_kernel(
 
         for (int c = jd.class_begin; c < jd.class_end; ++c) {
             const VamdClassDesc cd = classes[c];
-            const float* ext = (cd.flags & 1) ? extra : nullptr;
-            const float* b = (cd.bias_row >= 0 && bias_rows)
-                ? bias_rows + (size_t)cd.bias_row * N : bias;
+            const VamdClassPlanes pl =
+                class_planes(cd, extra, bias, bias_rows, N);
 
-            score_pass(tid, SC_THREADS, alloc, used, ext, ready, taints,
+            score_pass(tid, SC_THREADS, alloc, used, pl.ext, ready, taints,
                        planes, class_req + (size_t)c * R, class_tol[c],
                        class_require + (size_t)c * W,
                        class_forbid + (size_t)c * W,
-                       cd.w_least, cd.w_most, cd.w_bal, dim_w, b,
+                       cd.w_least, cd.w_most, cd.w_bal, dim_w, pl.bias,
                        score, cap, N, R, W);
             __syncthreads();
 
-            int fuse_min = -1;
-            if (single) {
-                int need = jd.min_available - jd.occupied;
-                if (cd.min_needed > need) need = cd.min_needed;
-                fuse_min = need > 0 ? need : 0;
-            }
+            const int fuse_min = single ? gang_fuse_min(jd, cd) : -1;
             dev_select_commit(score, cap, class_req + (size_t)c * R,
                               cd.ntasks, used,
                               queue_alloc + (size_t)cd.queue_idx * R,
@@ -1245,16 +1233,14 @@ __global__ void batch_score_kernel(
 {
     const int c = c0 + blockIdx.y;
     const VamdClassDesc cd = classes[c];
-    const float* ext = (cd.flags & 1) ? extra : nullptr;
-    const float* b = (cd.bias_row >= 0 && bias_rows)
-        ? bias_rows + (size_t)cd.bias_row * N : bias;
+    const VamdClassPlanes pl = class_planes(cd, extra, bias, bias_rows, N);
     score_pass(blockIdx.x * blockDim.x + threadIdx.x,
                gridDim.x * blockDim.x,
-               alloc, used, ext, ready, taints, planes,
+               alloc, used, pl.ext, ready, taints, planes,
                class_req + (size_t)c * R, class_tol[c],
                class_require + (size_t)c * W,
                class_forbid + (size_t)c * W,
-               cd.w_least, cd.w_most, cd.w_bal, dim_w, b,
+               cd.w_least, cd.w_most, cd.w_bal, dim_w, pl.bias,
                score_buf + (size_t)blockIdx.y * N, nullptr, N, R, W);
 }
 
@@ -1371,20 +1357,19 @@ select_chain_kernel(
         const VamdClassDesc cd = classes[c];
         const VamdJobDesc jd = jobs[cd.job_idx];
         const float* req = class_req + (size_t)c * R;
-        const float* ext = (cd.flags & 1) ? extra : nullptr;
-        const float* b = (cd.bias_row >= 0 && bias_rows)
-            ? bias_rows + (size_t)cd.bias_row * N : bias;
+        const VamdClassPlanes pl = class_planes(cd, extra, bias, bias_rows, N);
+        const float* ext = pl.ext;
+        const float* b = pl.bias;
         const float* row = score_buf + (size_t)(c - c0) * N;
         float* qa = queue_alloc + (size_t)cd.queue_idx * R;
         const float* ql = queue_limit + (size_t)cd.queue_idx * R;
         int* ln = log_nodes + cd.log_off;
         int* lc = log_counts + cd.log_off;
         const int K = cd.log_cap;
-        int fuse = jd.min_available - jd.occupied;
-        if (cd.min_needed > fuse) fuse = cd.min_needed;
-        if (fuse < 0) fuse = 0;
+        const int fuse = gang_fuse_min(jd, cd);
 
-        // queue quota — per-dim candidates on lanes < R, wave min-reduce
+        // queue quota (dev_queue_budget, lane-parallel) — per-dim
+        // candidates on lanes < R, wave min-reduce
         // (sequential dependent L2 loads cost ~300 ns each; the wave does
         // them in one round).  Every wave computes the same values from
         // the same memory → block-uniform without a barrier.
@@ -1681,25 +1666,19 @@ void vamd_domain_count_add(
                        log_len, dom_of, dom_count, D, N, K);
 }
 
-void vamd_batch_score(
-    const VamdClassDesc* classes_dev, int c0, int count,
-    const float* alloc, const float* used, const float* extra,
-    const uint8_t* ready, const int64_t* taints, const int64_t* planes,
-    const float* bias, const float* bias_rows,
-    const float* class_req, const int64_t* class_tol_dev,
-    const int64_t* class_require, const int64_t* class_forbid,
-    const float* dim_w, float* score_buf,
-    int N, int R, int W, hipStream_t stream)
+void vamd_batch_score(const VamdCycle& cy, const VamdDevDescs& dd, int c0,
+                      int count, float* score_buf, hipStream_t stream)
 {
     int threads = 256;
-    int nx = (N + threads - 1) / threads;
+    int nx = (cy.N + threads - 1) / threads;
     if (nx > 1024) nx = 1024;
     if (nx < 1) nx = 1;
     hipLaunchKernelGGL(vamd::batch_score_kernel, dim3(nx, count),
-                       dim3(threads), 0, stream, classes_dev, c0, alloc,
-                       used, extra, ready, taints, planes, bias, bias_rows,
-                       class_req, class_tol_dev, class_require, class_forbid,
-                       dim_w, score_buf, N, R, W);
+                       dim3(threads), 0, stream, dd.classes, c0, cy.alloc,
+                       cy.used, cy.extra, cy.ready, cy.taints, cy.planes,
+                       cy.bias, cy.bias_rows, cy.class_req, dd.class_tol,
+                       cy.class_require, cy.class_forbid, cy.dim_w,
+                       score_buf, cy.N, cy.R, cy.W);
 }
 
 void vamd_topk(float* score_buf, int count, float* topk_vals, int* topk_ids,
@@ -1709,54 +1688,34 @@ void vamd_topk(float* score_buf, int count, float* topk_vals, int* topk_ids,
                        stream, score_buf, topk_vals, topk_ids, N);
 }
 
-void vamd_select_chain(
-    const VamdClassDesc* classes_dev, const VamdJobDesc* jobs_dev,
-    int c0, int c1,
-    const float* alloc, float* used, const float* extra,
-    const uint8_t* ready, const int64_t* taints, const int64_t* planes,
-    const float* bias, const float* bias_rows,
-    const float* class_req, const int64_t* class_tol_dev,
-    const int64_t* class_require, const int64_t* class_forbid,
-    const float* dim_w,
-    float* queue_alloc, const float* queue_limit,
-    float* score_buf, const float* topk_vals, const int* topk_ids,
-    int* log_nodes, int* log_counts, int* log_len,
-    int* class_placed, int* job_placed,
-    uint8_t* touched, int* touched_list,
-    int N, int R, int W, hipStream_t stream)
+void vamd_select_chain(const VamdCycle& cy, const VamdDevDescs& dd, int c0,
+                       int c1, float* score_buf, const float* topk_vals,
+                       const int* topk_ids, uint8_t* touched,
+                       int* touched_list, hipStream_t stream)
 {
     hipLaunchKernelGGL(vamd::select_chain_kernel, dim3(1), dim3(CH_THREADS),
-                       0, stream, classes_dev, jobs_dev, c0, c1, alloc, used,
-                       extra, ready, taints, planes, bias, bias_rows,
-                       class_req, class_tol_dev, class_require, class_forbid,
-                       dim_w, queue_alloc, queue_limit, score_buf,
-                       topk_vals, topk_ids, log_nodes,
-                       log_counts, log_len, class_placed, job_placed,
-                       touched, touched_list, N, R, W);
+                       0, stream, dd.classes, dd.jobs, c0, c1, cy.alloc,
+                       cy.used, cy.extra, cy.ready, cy.taints, cy.planes,
+                       cy.bias, cy.bias_rows, cy.class_req, dd.class_tol,
+                       cy.class_require, cy.class_forbid, cy.dim_w,
+                       cy.queue_alloc, cy.queue_limit, score_buf, topk_vals,
+                       topk_ids, cy.log_nodes, cy.log_counts, cy.log_len,
+                       cy.class_placed, cy.job_placed, touched, touched_list,
+                       cy.N, cy.R, cy.W);
 }
 
-void vamd_megacycle(
-    const VamdClassDesc* classes_dev, const VamdJobDesc* jobs_dev,
-    int n_jobs,
-    const float* alloc, float* used, const float* extra,
-    const uint8_t* ready, const int64_t* taints, const int64_t* planes,
-    const float* bias, const float* bias_rows,
-    const float* class_req, const int64_t* class_tol_dev,
-    const int64_t* class_require, const int64_t* class_forbid,
-    const int32_t* class_min, const float* dim_w,
-    float* queue_alloc, const float* queue_limit,
-    float* score_scratch, int* cap_scratch,
-    int* log_nodes, int* log_counts, int* log_len,
-    int* class_placed, int* job_placed, uint8_t* job_flag,
-    int N, int R, int W, hipStream_t stream)
+void vamd_megacycle(const VamdCycle& cy, const VamdDevDescs& dd,
+                    hipStream_t stream)
 {
     hipLaunchKernelGGL(vamd::megacycle_kernel, dim3(1), dim3(SC_THREADS), 0,
-                       stream, classes_dev, jobs_dev, n_jobs, alloc, used,
-                       extra, ready, taints, planes, bias, bias_rows,
-                       class_req, class_tol_dev, class_require, class_forbid,
-                       class_min, dim_w, queue_alloc, queue_limit,
-                       score_scratch, cap_scratch, log_nodes, log_counts,
-                       log_len, class_placed, job_placed, job_flag, N, R, W);
+                       stream, dd.classes, dd.jobs, cy.n_jobs, cy.alloc,
+                       cy.used, cy.extra, cy.ready, cy.taints, cy.planes,
+                       cy.bias, cy.bias_rows, cy.class_req, dd.class_tol,
+                       cy.class_require, cy.class_forbid, cy.class_min,
+                       cy.dim_w, cy.queue_alloc, cy.queue_limit,
+                       cy.score_scratch, cy.cap_scratch, cy.log_nodes,
+                       cy.log_counts, cy.log_len, cy.class_placed,
+                       cy.job_placed, cy.job_flag, cy.N, cy.R, cy.W);
 }
 
 }  // extern "C"

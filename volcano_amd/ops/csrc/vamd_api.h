@@ -108,150 +108,129 @@ struct VamdJobDesc {
     int32_t min_available;
 };
 
+// Shared by the runner (host) and the megacycle / chain kernels (device).
+#if defined(__HIPCC__)
+#define VAMD_HD __host__ __device__
+#else
+#define VAMD_HD
+#endif
+
+// Gang minimum of a single-class job, fused into its select: how many more
+// tasks the job needs to become ready (min_available - occupied), never
+// less than the class's own role minimum, never negative.
+VAMD_HD inline int gang_fuse_min(const VamdJobDesc& job,
+                                 const VamdClassDesc& cd) {
+    int need = job.min_available - job.occupied;
+    if (cd.min_needed > need) need = cd.min_needed;
+    return need > 0 ? need : 0;
+}
+
+// Future-idle credit plane (flags bit0) and bias plane of a class: its own
+// row of bias_rows (task-topology bucket packing) overrides the plan bias.
+struct VamdClassPlanes { const float* ext; const float* bias; };
+
+VAMD_HD inline VamdClassPlanes class_planes(
+    const VamdClassDesc& cd, const float* extra, const float* bias,
+    const float* bias_rows, int N) {
+    return {(cd.flags & 1) ? extra : nullptr,
+            (cd.bias_row >= 0 && bias_rows)
+                ? bias_rows + (size_t)cd.bias_row * N : bias};
+}
+
+// Everything one allocate cycle reads and writes.  Device pointers unless
+// marked HOST; C = n_classes, J = n_jobs.
+struct VamdCycle {
+    uint64_t struct_size;          // sizeof(VamdCycle), checked on entry
+    int32_t N, R, W;
+    int32_t n_classes, n_jobs;
+    int32_t _pad;
+    const VamdClassDesc* classes;  // HOST [C]
+    const VamdJobDesc* jobs;       // HOST [J]
+    // node state [R, N] (+ masks)
+    const float* alloc;
+    float* used;
+    const float* extra;
+    const uint8_t* ready;          // [N]
+    const int64_t* taints;         // [N]
+    const int64_t* planes;         // [W, N]
+    const float* bias;             // [N] plan-wide (nullable)
+    const float* bias_rows;        // [B, N] per-class rows (nullable)
+    // per-class constraint rows
+    const float* class_req;        // [C, R]
+    const int64_t* class_tol;      // HOST [C]
+    const int64_t* class_require;  // [C, W]
+    const int64_t* class_forbid;   // [C, W]
+    const int32_t* class_min;      // [C] (device copy of min_needed, for finalize)
+    const float* dim_w;            // [R]
+    // queue state
+    float* queue_alloc;            // [Q, R]
+    const float* queue_limit;      // [Q, R]
+    // outputs / scratch
+    float* score_scratch;          // [N]
+    int* cap_scratch;              // [N]
+    int* log_nodes;                // [L]
+    int* log_counts;               // [L]
+    int* log_len;                  // [C]
+    int* class_placed;             // [C]
+    int* job_placed;               // [J]
+    uint8_t* job_flag;             // [J]
+    unsigned* sort_scratch;        // [4N] bulk-select radix scratch (nullable)
+    // domain-rule block (topology spread, inter-pod (anti-)affinity): live
+    // only when class_group, dom_of, count and domain_scratch are all set
+    const int32_t* class_group;    // HOST [C]: group index or -1
+    const int32_t* class_skew;     // HOST [C]: maxSkew (>= 1, mode 0)
+    const int32_t* class_mode;     // HOST [C]: 0 / 1 / 2; null = all 0
+    const int32_t* dom_of;         // [G, N]
+    int32_t* count;                // groups back to back
+    const int32_t* count_off;      // HOST [G]: offset into count
+    const int32_t* domains;        // HOST [G]: D of each group
+    void* domain_scratch;          // 12*N bytes, 8-aligned
+};
+
+// Device copies of the descriptor arrays (chain and megacycle paths).
+struct VamdDevDescs {
+    const VamdClassDesc* classes;  // [C]
+    const VamdJobDesc* jobs;       // [J]
+    const int64_t* class_tol;      // [C]
+};
+
+// Chain path (heterogeneous mixes): batch-score a chunk of consecutive
+// single-class jobs against chunk-start usage, then replay their selects
+// in one launch with lazy exact re-scoring of touched nodes.  Decisions
+// are bit-identical to the per-class path (see scheduler_kernels.hip).
+// These three are called by the runner only.
+void vamd_batch_score(const VamdCycle& cy, const VamdDevDescs& dd, int c0,
+                      int count, float* score_buf, hipStream_t stream);
+
+void vamd_topk(float* score_buf, int count, float* topk_vals, int* topk_ids,
+               int N, hipStream_t stream);
+
+void vamd_select_chain(const VamdCycle& cy, const VamdDevDescs& dd, int c0,
+                       int c1, float* score_buf, const float* topk_vals,
+                       const int* topk_ids, uint8_t* touched,
+                       int* touched_list, hipStream_t stream);
+
+// One launch for a whole small-class plan (heterogeneous shapes).
+void vamd_megacycle(const VamdCycle& cy, const VamdDevDescs& dd,
+                    hipStream_t stream);
+
 // Executes a whole allocate cycle: for each job (in the host-given order),
 // for each of its classes: score_cap + select_commit; then the gang
 // finalize/revert.  Single-class jobs fuse the gang check into
 // select_commit (2 launches per job).  Everything stays on `stream`;
 // NO host synchronisation happens here.
-// Chain path (heterogeneous mixes): batch-score a chunk of consecutive
-// single-class jobs against chunk-start usage, then replay their selects
-// in one launch with lazy exact re-scoring of touched nodes.  Decisions
-// are bit-identical to the per-class path (see scheduler_kernels.hip).
-// Descriptor/taint arrays must be DEVICE pointers.
-void vamd_batch_score(
-    const VamdClassDesc* classes_dev, int c0, int count,
-    const float* alloc, const float* used, const float* extra,
-    const uint8_t* ready, const int64_t* taints, const int64_t* planes,
-    const float* bias, const float* bias_rows,
-    const float* class_req, const int64_t* class_tol_dev,
-    const int64_t* class_require, const int64_t* class_forbid,
-    const float* dim_w, float* score_buf,
-    int N, int R, int W, hipStream_t stream);
-
-void vamd_topk(float* score_buf, int count, float* topk_vals, int* topk_ids,
-               int N, hipStream_t stream);
-
-void vamd_select_chain(
-    const VamdClassDesc* classes_dev, const VamdJobDesc* jobs_dev,
-    int c0, int c1,
-    const float* alloc, float* used, const float* extra,
-    const uint8_t* ready, const int64_t* taints, const int64_t* planes,
-    const float* bias, const float* bias_rows,
-    const float* class_req, const int64_t* class_tol_dev,
-    const int64_t* class_require, const int64_t* class_forbid,
-    const float* dim_w,
-    float* queue_alloc, const float* queue_limit,
-    float* score_buf, const float* topk_vals, const int* topk_ids,
-    int* log_nodes, int* log_counts, int* log_len,
-    int* class_placed, int* job_placed,
-    uint8_t* touched, int* touched_list,
-    int N, int R, int W, hipStream_t stream);
-
-// One launch for a whole small-class plan (heterogeneous shapes):
-// descriptor/taint arrays must be DEVICE pointers here.
-void vamd_megacycle(
-    const VamdClassDesc* classes_dev, const VamdJobDesc* jobs_dev,
-    int n_jobs,
-    const float* alloc, float* used, const float* extra,
-    const uint8_t* ready, const int64_t* taints, const int64_t* planes,
-    const float* bias, const float* bias_rows,
-    const float* class_req, const int64_t* class_tol_dev,
-    const int64_t* class_require, const int64_t* class_forbid,
-    const int32_t* class_min, const float* dim_w,
-    float* queue_alloc, const float* queue_limit,
-    float* score_scratch, int* cap_scratch,
-    int* log_nodes, int* log_counts, int* log_len,
-    int* class_placed, int* job_placed, uint8_t* job_flag,
-    int N, int R, int W, hipStream_t stream);
-
-void vamd_run_cycle(
-    const VamdClassDesc* classes, int n_classes,
-    const VamdJobDesc* jobs, int n_jobs,
-    // node state [R, N] (+ masks)
-    const float* alloc, float* used, const float* extra,
-    const uint8_t* ready, const int64_t* taints, const int64_t* planes,
-    const float* bias,
-    const float* bias_rows,        // [B, N] per-class rows (nullable)
-    // per-class constraint rows
-    const float* class_req,        // [C, R]
-    const int64_t* class_tol,      // [C]
-    const int64_t* class_require,  // [C, W]
-    const int64_t* class_forbid,   // [C, W]
-    const int32_t* class_min,      // [C] (device copy of min_needed, for finalize)
-    const float* dim_w,            // [R]
-    // queue state
-    float* queue_alloc,            // [Q, R]
-    const float* queue_limit,      // [Q, R]
-    // outputs / scratch
-    float* score_scratch,          // [N]
-    int* cap_scratch,              // [N]
-    int* log_nodes, int* log_counts, int* log_len,  // [L], [L], [C]
-    int* class_placed,             // [C]
-    int* job_placed,               // [J]
-    uint8_t* job_flag,             // [J]
-    unsigned* sort_scratch,        // [4N] bulk-select radix scratch (nullable)
-    int N, int R, int W,
-    hipStream_t stream);
-
-// vamd_run_cycle for plans with topology-spread classes.  A spread class
-// (class_spread_group[c] >= 0) always runs vamd_score_cap +
-// vamd_spread_select — never the fused, bulk, chain or megacycle path —
-// and reverts through vamd_spread_revert.  Counts carry across the
-// classes of a group in plan order and stay on the device.  With
-// class_spread_group == nullptr (or all -1) this IS vamd_run_cycle:
-// the same launches in the same order.
-void vamd_run_cycle_spread(
-    const VamdClassDesc* classes, int n_classes,
-    const VamdJobDesc* jobs, int n_jobs,
-    const float* alloc, float* used, const float* extra,
-    const uint8_t* ready, const int64_t* taints, const int64_t* planes,
-    const float* bias, const float* bias_rows,
-    const float* class_req, const int64_t* class_tol,
-    const int64_t* class_require, const int64_t* class_forbid,
-    const int32_t* class_min, const float* dim_w,
-    float* queue_alloc, const float* queue_limit,
-    float* score_scratch, int* cap_scratch,
-    int* log_nodes, int* log_counts, int* log_len,
-    int* class_placed, int* job_placed, uint8_t* job_flag,
-    unsigned* sort_scratch,
-    int N, int R, int W,
-    const int32_t* class_spread_group,  // HOST [C]: group index or -1
-    const int32_t* class_spread_skew,   // HOST [C]: maxSkew (>= 1)
-    const int32_t* spread_dom_of,       // device [G, N]
-    int32_t* spread_count,              // device, groups back to back
-    const int32_t* spread_count_off,    // HOST [G]: offset into spread_count
-    const int32_t* spread_domains,      // HOST [G]: D of each group
-    void* spread_scratch,               // device, 12*N bytes, 8-aligned
-    hipStream_t stream);
-
-// vamd_run_cycle_spread plus a per-class mode column: 0 = topology spread
-// (as above), 1 = inter-pod affinity, 2 = keyed anti-affinity over the
-// class's group.  An affinity / anti class always runs vamd_score_cap ->
-// vamd_domain_mask -> vamd_select_commit (bulk by size, given
-// sort_scratch) -> vamd_domain_count_add: a launch count constant in
-// ntasks, never the fused, chain or megacycle path, and it reverts
-// through vamd_spread_revert.  With class_domain_mode == nullptr (or all
-// 0) this IS vamd_run_cycle_spread.
-void vamd_run_cycle_domains(
-    const VamdClassDesc* classes, int n_classes,
-    const VamdJobDesc* jobs, int n_jobs,
-    const float* alloc, float* used, const float* extra,
-    const uint8_t* ready, const int64_t* taints, const int64_t* planes,
-    const float* bias, const float* bias_rows,
-    const float* class_req, const int64_t* class_tol,
-    const int64_t* class_require, const int64_t* class_forbid,
-    const int32_t* class_min, const float* dim_w,
-    float* queue_alloc, const float* queue_limit,
-    float* score_scratch, int* cap_scratch,
-    int* log_nodes, int* log_counts, int* log_len,
-    int* class_placed, int* job_placed, uint8_t* job_flag,
-    unsigned* sort_scratch,
-    int N, int R, int W,
-    const int32_t* class_spread_group,  // HOST [C]: group index or -1
-    const int32_t* class_spread_skew,   // HOST [C]: maxSkew (mode 0)
-    const int32_t* class_domain_mode,   // HOST [C]: 0 / 1 / 2
-    const int32_t* spread_dom_of, int32_t* spread_count,
-    const int32_t* spread_count_off, const int32_t* spread_domains,
-    void* spread_scratch, hipStream_t stream);
+//   * A spread class (class_group[c] >= 0, mode 0) always runs
+//     vamd_score_cap + vamd_spread_select — never the fused, bulk, chain
+//     or megacycle path — and reverts through vamd_spread_revert.  Counts
+//     carry across the classes of a group in plan order, on the device.
+//   * An affinity (mode 1) / keyed anti-affinity (mode 2) class always
+//     runs vamd_score_cap -> vamd_domain_mask -> vamd_select_commit (bulk
+//     by size, given sort_scratch) -> vamd_domain_count_add: a launch
+//     count constant in ntasks; it reverts through vamd_spread_revert.
+//   * With the domain block dead (or every group -1) nothing above
+//     changes a single launch.
+// Returns 0; nonzero, before any HIP call, when cy->struct_size is not
+// sizeof(VamdCycle).
+int vamd_run_cycle(const VamdCycle* cy, hipStream_t stream);
 
 }  // extern "C"

@@ -9,7 +9,8 @@ are the CPU oracle, not a GPU execution path).
 from __future__ import annotations
 
 import ctypes
-from ctypes import (Structure, c_float, c_int, c_int32, c_int64, c_void_p)
+from ctypes import (POINTER, Structure, c_float, c_int, c_int32, c_int64,
+                    c_uint64, c_void_p)
 from typing import Optional
 
 import torch
@@ -36,6 +37,23 @@ class VamdJobDesc(Structure):
     ]
 
 
+class VamdCycle(Structure):
+    """Mirror of ``VamdCycle`` in ``vamd_api.h`` (same order, same types)."""
+    _fields_ = [("struct_size", c_uint64)] + [
+        (n, c_int32) for n in ("N", "R", "W", "n_classes", "n_jobs", "_pad")
+    ] + [(n, c_void_p) for n in (
+        "classes", "jobs",
+        "alloc", "used", "extra", "ready", "taints", "planes",
+        "bias", "bias_rows",
+        "class_req", "class_tol", "class_require", "class_forbid",
+        "class_min", "dim_w",
+        "queue_alloc", "queue_limit",
+        "score_scratch", "cap_scratch", "log_nodes", "log_counts", "log_len",
+        "class_placed", "job_placed", "job_flag", "sort_scratch",
+        "class_group", "class_skew", "class_mode", "dom_of", "count",
+        "count_off", "domains", "domain_scratch")]
+
+
 def _load():
     global _lib
     if _lib is not None:
@@ -53,15 +71,14 @@ def _load():
     lib.vamd_select_commit.restype = None
     lib.vamd_finalize_job.restype = None
     lib.vamd_cond_revert.restype = None
-    lib.vamd_run_cycle.restype = None
+    lib.vamd_run_cycle.argtypes = [POINTER(VamdCycle), c_void_p]
+    lib.vamd_run_cycle.restype = c_int
     lib.vamd_fused_score_select.restype = None
     lib.vamd_topk.restype = None
     lib.vamd_spread_select.restype = None
     lib.vamd_spread_revert.restype = None
-    lib.vamd_run_cycle_spread.restype = None
     lib.vamd_domain_mask.restype = None
     lib.vamd_domain_count_add.restype = None
-    lib.vamd_run_cycle_domains.restype = None
     _lib = lib
     return lib
 
@@ -74,8 +91,12 @@ def available() -> bool:
         return False
 
 
+def _addr(t: Optional[torch.Tensor]) -> int:
+    return 0 if t is None else t.data_ptr()
+
+
 def _p(t: Optional[torch.Tensor]):
-    return c_void_p(0 if t is None else t.data_ptr())
+    return c_void_p(_addr(t))
 
 
 def _stream() -> c_void_p:
@@ -260,63 +281,51 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
               spread=None):
     """One library call = one whole allocate cycle (plan built host-side).
 
-    ``spread`` (plans with topology-spread classes only) is a dict:
+    ``class_descs`` / ``job_descs`` are host buffers of ``VamdClassDesc`` /
+    ``VamdJobDesc``; ``class_tol`` is a host tensor, every other tensor is
+    on the device.
+
+    ``spread`` (plans with domain-rule classes only) is a dict:
     ``class_group``/``class_skew`` host int32 numpy [C], ``dom_of`` device
     i32 [G, N], ``count`` device i32 (groups back to back), ``count_off``/
     ``domains`` host int32 numpy [G], ``scratch`` device
     (``spread_scratch``).  An optional ``class_mode`` (host int32 numpy
-    [C]: 0 spread, 1 inter-pod affinity, 2 keyed anti-affinity) routes the
-    call through ``vamd_run_cycle_domains``."""
+    [C]: 0 spread, 1 inter-pod affinity, 2 keyed anti-affinity) fills the
+    mode column; without it every class of a group is a spread class."""
     lib = _load()
     R, N = alloc_t.shape
-    W = planes_t.shape[0]
-    if spread is not None and spread.get("class_mode") is not None:
-        mode = spread["class_mode"]
-        if mode.shape[0] != n_classes or mode.dtype != "int32":
-            raise ValueError("run_cycle: class_mode must be int32 [C]")
-        lib.vamd_run_cycle_domains(
-            class_descs, c_int(n_classes),
-            job_descs, c_int(n_jobs),
-            _p(alloc_t), _p(used_t), _p(extra_t), _p(ready), _p(taints),
-            _p(planes_t), _p(bias), _p(bias_rows), _p(class_req),
-            _p(class_tol), _p(class_require), _p(class_forbid),
-            _p(class_min), _p(dim_w), _p(queue_alloc), _p(queue_limit),
-            _p(score_scratch), _p(cap_scratch), _p(log_nodes),
-            _p(log_counts), _p(log_len), _p(class_placed), _p(job_placed),
-            _p(job_flag), _p(sort_scratch), c_int(N), c_int(R), c_int(W),
-            c_void_p(spread["class_group"].ctypes.data),
-            c_void_p(spread["class_skew"].ctypes.data),
-            c_void_p(mode.ctypes.data),
-            _p(spread["dom_of"]), _p(spread["count"]),
-            c_void_p(spread["count_off"].ctypes.data),
-            c_void_p(spread["domains"].ctypes.data),
-            _p(spread["scratch"]), _stream())
-        return
+    cy = VamdCycle(
+        struct_size=ctypes.sizeof(VamdCycle), N=N, R=R, W=planes_t.shape[0],
+        n_classes=n_classes, n_jobs=n_jobs,
+        classes=ctypes.cast(class_descs, c_void_p),
+        jobs=ctypes.cast(job_descs, c_void_p),
+        alloc=_addr(alloc_t), used=_addr(used_t), extra=_addr(extra_t),
+        ready=_addr(ready), taints=_addr(taints), planes=_addr(planes_t),
+        bias=_addr(bias), bias_rows=_addr(bias_rows),
+        class_req=_addr(class_req), class_tol=_addr(class_tol),
+        class_require=_addr(class_require), class_forbid=_addr(class_forbid),
+        class_min=_addr(class_min), dim_w=_addr(dim_w),
+        queue_alloc=_addr(queue_alloc), queue_limit=_addr(queue_limit),
+        score_scratch=_addr(score_scratch), cap_scratch=_addr(cap_scratch),
+        log_nodes=_addr(log_nodes), log_counts=_addr(log_counts),
+        log_len=_addr(log_len), class_placed=_addr(class_placed),
+        job_placed=_addr(job_placed), job_flag=_addr(job_flag),
+        sort_scratch=_addr(sort_scratch))
     if spread is not None:
-        lib.vamd_run_cycle_spread(
-            class_descs, c_int(n_classes),
-            job_descs, c_int(n_jobs),
-            _p(alloc_t), _p(used_t), _p(extra_t), _p(ready), _p(taints),
-            _p(planes_t), _p(bias), _p(bias_rows), _p(class_req),
-            _p(class_tol), _p(class_require), _p(class_forbid),
-            _p(class_min), _p(dim_w), _p(queue_alloc), _p(queue_limit),
-            _p(score_scratch), _p(cap_scratch), _p(log_nodes),
-            _p(log_counts), _p(log_len), _p(class_placed), _p(job_placed),
-            _p(job_flag), _p(sort_scratch), c_int(N), c_int(R), c_int(W),
-            c_void_p(spread["class_group"].ctypes.data),
-            c_void_p(spread["class_skew"].ctypes.data),
-            _p(spread["dom_of"]), _p(spread["count"]),
-            c_void_p(spread["count_off"].ctypes.data),
-            c_void_p(spread["domains"].ctypes.data),
-            _p(spread["scratch"]), _stream())
-        return
-    lib.vamd_run_cycle(
-        class_descs, c_int(n_classes),
-        job_descs, c_int(n_jobs),
-        _p(alloc_t), _p(used_t), _p(extra_t), _p(ready), _p(taints),
-        _p(planes_t), _p(bias), _p(bias_rows), _p(class_req), _p(class_tol),
-        _p(class_require), _p(class_forbid), _p(class_min), _p(dim_w),
-        _p(queue_alloc), _p(queue_limit), _p(score_scratch), _p(cap_scratch),
-        _p(log_nodes), _p(log_counts), _p(log_len), _p(class_placed),
-        _p(job_placed), _p(job_flag), _p(sort_scratch),
-        c_int(N), c_int(R), c_int(W), _stream())
+        mode = spread.get("class_mode")
+        if mode is not None:
+            if mode.shape[0] != n_classes or mode.dtype != "int32":
+                raise ValueError("run_cycle: class_mode must be int32 [C]")
+            cy.class_mode = mode.ctypes.data
+        cy.class_group = spread["class_group"].ctypes.data
+        cy.class_skew = spread["class_skew"].ctypes.data
+        cy.dom_of = _addr(spread["dom_of"])
+        cy.count = _addr(spread["count"])
+        cy.count_off = spread["count_off"].ctypes.data
+        cy.domains = spread["domains"].ctypes.data
+        cy.domain_scratch = _addr(spread["scratch"])
+    rc = lib.vamd_run_cycle(ctypes.byref(cy), _stream())
+    if rc != 0:
+        raise RuntimeError(
+            f"vamd_run_cycle rejected the call (rc={rc}): the loaded "
+            "library and this module disagree on the VamdCycle layout")
