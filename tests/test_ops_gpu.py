@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+import _kernel_cases as kc
+
 pytestmark = pytest.mark.gpu
 
 ref = pytest.importorskip("volcano_amd.ops.reference")
@@ -43,13 +45,14 @@ def test_score_cap_matches_oracle(hip, seed, N, R):
     # R > 16 guards the regression where a fixed frac[16] register array
     # overflowed per-thread scratch once synthetic dims (paa:/hp:) grew
     # the registry past 16
-    st = rand_state(N=N, R=R, seed=seed)
+    assert (N, R) in kc.RAND_SCORE_SHAPES and seed in kc.RAND_SCORE_SEEDS
+    st, weights, masks = kc.rand_score_case(rand_state, N, R, seed)
+    assert weights == dict(w_least=1.0, w_most=0.7, w_bal=0.3)
     R = st["req"].shape[0]
     W = st["planes"].shape[1]
-    require = torch.tensor([0b1010, 0], dtype=torch.int64)
-    forbid = torch.tensor([0b0100, 0], dtype=torch.int64)
-    dim_w = torch.rand(R) + 0.5
-    tol = 0b01
+    require, forbid, tol = masks["require"], masks["forbid"], \
+        masks["tolerated"]
+    dim_w = st["dim_w"]
 
     score_c = torch.empty(N)
     cap_c = torch.empty(N, dtype=torch.int32)
@@ -79,6 +82,12 @@ def test_score_cap_matches_oracle(hip, seed, N, R):
     assert torch.equal(cap_c, cap_g), "capacity mismatch"
     assert torch.allclose(score_c[feas_c], score_g[feas_g], atol=1e-4,
                           rtol=1e-4), "score mismatch"
+    # and against the float64 formula, within the bound the CPU tier
+    # measures for exactly these inputs (tests/test_inexact_cases.py)
+    want = kc.score_f64(st, **weights)
+    err = float(np.abs(score_g.double().numpy() - want)[feas_g.numpy()].max())
+    print(f"score error vs float64: {err:.3e}")
+    assert err <= kc.RAND_KERNEL_ERR, err
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2, 3])

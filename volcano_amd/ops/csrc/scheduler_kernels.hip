@@ -211,10 +211,26 @@ DEVINL long long dev_queue_budget(
     return min((long long)ntasks, quota);
 }
 
-// Commit epilogue of the log-first selects (bulk, spread), whole 1024-
-// thread block: ONE (float)count * req per log entry goes into `used`
-// (a wave per entry), the class total into queue_alloc, then the counters
-// are published.
+// count * req joins (sign > 0) or leaves (sign < 0) an accumulator in ONE
+// rounding.  Spelled out so that every commit and every revert site of
+// every kernel compiles the same operation, whatever the compiler would
+// contract in that inlining context: the selects must leave bit-equal
+// usage, and a revert must subtract exactly what its commit added.
+DEVINL float acc_add(float acc, int count, float req) {
+    return fmaf((float)count, req, acc);
+}
+DEVINL float acc_sub(float acc, int count, float req) {
+    return fmaf(-(float)count, req, acc);
+}
+
+// Commit epilogue of every select (serial, bulk, spread), whole 1024-
+// thread block: ONE count * req per log entry goes into `used` (a wave per
+// entry), the class total into queue_alloc, then the counters are
+// published.  All selects are log-first: nothing touches `used` or
+// queue_alloc before this point, so a single-class gang that misses its
+// minimum (fuse_min) is discarded by simply not calling it — no
+// add-then-subtract, whose f32 result is not the starting value once
+// usage comes in bytes.
 DEVINL void dev_commit_log(
     const int* __restrict__ log_nodes, const int* __restrict__ log_counts,
     int len, int total, const float* __restrict__ req,
@@ -227,9 +243,12 @@ DEVINL void dev_commit_log(
     for (int e = tid / WAVE; e < len; e += 1024 / WAVE) {
         int node = log_nodes[e];
         int cnt = log_counts[e];
-        if (lane < R) used[(size_t)lane * N + node] += (float)cnt * req[lane];
+        if (lane < R) {
+            float* u = used + (size_t)lane * N + node;
+            *u = acc_add(*u, cnt, req[lane]);
+        }
     }
-    if (tid < R) queue_alloc[tid] += (float)total * req[tid];
+    if (tid < R) queue_alloc[tid] = acc_add(queue_alloc[tid], total, req[tid]);
     if (tid == 0) {
         *log_len = len;
         *placed = total;
@@ -242,9 +261,10 @@ DEVINL void dev_commit_log(
 //   ONE workgroup (1024 threads = 16 waves).  Iterative argmax over the
 //   score vector with per-thread cached local maxima: after node b is
 //   consumed only its owner thread rescans its stride (N/1024 elements,
-//   L2-resident).  Updates used/queue_alloc/job accounting in place and
-//   writes an undo log; optionally performs the single-class gang revert
-//   in-kernel (fuse_min >= 0).
+//   L2-resident).  The loop only writes the undo log (it never reads
+//   `used`); usage, queue_alloc and the job accounting are committed from
+//   the log afterwards (dev_commit_log) — or not at all when the single-
+//   class gang misses its minimum (fuse_min >= 0).
 // ---------------------------------------------------------------------------
 #define SC_THREADS 1024
 #define SC_WAVES (SC_THREADS / WAVE)
@@ -269,7 +289,6 @@ __device__ void dev_select_commit(
     __shared__ ValIdx s_best;
     __shared__ int s_remaining;
     __shared__ int s_cursor;
-    __shared__ int s_take;
     __shared__ int s_go;
     __shared__ long long s_budget;
 
@@ -317,18 +336,12 @@ __device__ void dev_select_commit(
         ValIdx best = s_best;
         if (!s_go) break;
 
-        // take is published through LDS for the same reason
         if (tid == 0) {
-            s_take = min(cap[best.i], s_remaining);
+            const int take = min(cap[best.i], s_remaining);
             log_nodes[s_cursor] = best.i;
-            log_counts[s_cursor] = s_take;
+            log_counts[s_cursor] = take;
             s_cursor += 1;
-            s_remaining -= s_take;
-        }
-        __syncthreads();
-        int take = s_take;
-        if (tid < R) {
-            used[(size_t)tid * N + best.i] += (float)take * req[tid];
+            s_remaining -= take;
         }
         // knock out the chosen node; its owner rescans its slice
         if (tid == (best.i & (SC_THREADS - 1))) {
@@ -346,23 +359,16 @@ __device__ void dev_select_commit(
     int total = (int)s_budget - s_remaining;
     bool revert = (fuse_min >= 0) && (total < fuse_min);
 
+    const int cursor = s_cursor;
+
     if (revert) {
-        // single-class gang failed: undo in place (statement.go:375 Discard)
-        for (int e = wid; e < s_cursor; e += SC_WAVES) {
-            int node = log_nodes[e];
-            int cnt = log_counts[e];
-            if (lane < R) used[(size_t)lane * N + node] -= (float)cnt * req[lane];
-            if (lane == 0) log_counts[e] = 0;
-        }
-        __syncthreads();
-        if (tid == 0) { *log_len = s_cursor; *placed = 0; }
+        // single-class gang failed (statement.go:375 Discard): nothing was
+        // applied, the log keeps its nodes with zeroed counts
+        for (int e = tid; e < cursor; e += SC_THREADS) log_counts[e] = 0;
+        if (tid == 0) { *log_len = cursor; *placed = 0; }
     } else {
-        if (tid < R) queue_alloc[tid] += (float)total * req[tid];
-        if (tid == 0) {
-            *log_len = s_cursor;
-            *placed = total;
-            *job_placed += total;
-        }
+        dev_commit_log(log_nodes, log_counts, cursor, total, req, used,
+                       queue_alloc, log_len, placed, job_placed, N, R);
     }
 }
 
@@ -467,12 +473,15 @@ __device__ void dev_cond_revert(
         int cnt = log_counts[e];
         if (cnt == 0) continue;
         int node = log_nodes[e];
-        if (lane_r < R)
-            used[(size_t)lane_r * N + node] -= (float)cnt * req[lane_r];
+        if (lane_r < R) {
+            float* u = used + (size_t)lane_r * N + node;
+            *u = acc_sub(*u, cnt, req[lane_r]);
+        }
     }
     if (tid == 0) {
         int p = *placed;
-        for (int r = 0; r < R; ++r) queue_alloc[r] -= (float)p * req[r];
+        for (int r = 0; r < R; ++r)
+            queue_alloc[r] = acc_sub(queue_alloc[r], p, req[r]);
         *job_placed -= p;
         *placed = 0;
     }
@@ -1490,8 +1499,10 @@ select_chain_kernel(
                 }
                 cursor += 1;
                 remaining -= take;
-                if (tid < R)
-                    used[(size_t)tid * N + best.i] += (float)take * req[tid];
+                // `used` waits for the end of the class: the winner is
+                // never a node this class already took (consumed nodes
+                // are skipped above), so nothing in this loop would read
+                // the new value, and a discarded gang then leaves no trace
             }
             if (!was_touched) {
                 // mark even on take==0 (defensive: a zero-cap winner must
@@ -1505,19 +1516,22 @@ select_chain_kernel(
             __syncthreads();    // barrier 2: order stores vs next loads
         }
 
+        // barrier 2 of the last pop ordered thread 0's log stores
         int total = (int)budget - remaining;
         if (total < fuse) {
-            // single-class gang revert (statement.go:375 Discard)
-            for (int e = 0; e < cursor; ++e) {
-                int node = ln[e];
-                int cnt = lc[e];
-                if (tid < R)
-                    used[(size_t)tid * N + node] -= (float)cnt * req[tid];
-                if (tid == 0) lc[e] = 0;
-            }
+            // single-class gang discard (statement.go:375): nothing was
+            // applied; the log keeps its nodes with zeroed counts
+            for (int e = tid; e < cursor; e += CH_THREADS) lc[e] = 0;
             if (tid == 0) { log_len[c] = cursor; class_placed[c] = 0; }
         } else {
-            if (tid < R) qa[tid] += (float)total * req[tid];
+            // commit from the log, a wave per entry (dev_commit_log)
+            for (int e = wid; e < cursor; e += CH_WAVES) {
+                if (lane < R) {
+                    float* u = used + (size_t)lane * N + ln[e];
+                    *u = acc_add(*u, lc[e], req[lane]);
+                }
+            }
+            if (tid < R) qa[tid] = acc_add(qa[tid], total, req[tid]);
             if (tid == 0) {
                 log_len[c] = cursor;
                 class_placed[c] = total;

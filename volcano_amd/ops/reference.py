@@ -40,6 +40,18 @@ EPS = 1e-4          # resource-fit slack, mirrors api/resource.MIN_RESOURCE scal
 BIG_CAP = 2 ** 30   # "unbounded" capacity sentinel
 
 
+def _row_sum(x: torch.Tensor) -> torch.Tensor:
+    """Sum over the resource dim, one column after the other (the kernel's
+    order).  ``x.sum(dim=1)`` vectorizes across rows and rounds a row
+    differently depending on where in the tensor it sits, so two nodes
+    with identical inputs could get different scores and a tie would no
+    longer go to the lower index; elementwise adds cannot do that."""
+    acc = torch.zeros(x.shape[0], dtype=x.dtype, device=x.device)
+    for r in range(x.shape[1]):
+        acc = acc + x[:, r]
+    return acc
+
+
 def score_cap(
     alloc: torch.Tensor,        # [N, R] f32 allocatable
     used: torch.Tensor,         # [N, R] f32 currently used (incl. staged)
@@ -76,10 +88,11 @@ def score_cap(
     denom = torch.clamp(alloc, min=EPS)
     frac = torch.clamp((used + req) / denom, max=1.0)         # [N, R]
     wsum = torch.clamp(dim_w.sum(), min=EPS)
-    least = ((1.0 - frac) * dim_w).sum(dim=1) / wsum
-    most = (frac * dim_w).sum(dim=1) / wsum
-    mean = frac.mean(dim=1, keepdim=True)
-    bal = 1.0 - torch.sqrt(((frac - mean) ** 2).mean(dim=1))
+    R = alloc.shape[1]
+    least = _row_sum((1.0 - frac) * dim_w) / wsum
+    most = _row_sum(frac * dim_w) / wsum
+    mean = (_row_sum(frac) / R).unsqueeze(1)
+    bal = 1.0 - torch.sqrt(_row_sum((frac - mean) ** 2) / R)
     score = w_least * least + w_most * most + w_bal * bal
     if bias is not None:
         score = score + bias

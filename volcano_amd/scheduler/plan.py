@@ -349,6 +349,12 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
                           cp.w_least, cp.w_most, cp.w_bal, dim_w, b,
                           score, cap)
             sl = slice(cp.log_off, cp.log_off + cp.log_cap)
+            if single:
+                # a discarded single-class gang leaves no trace (the HIP
+                # selects commit from the log only when the gang holds):
+                # u + c*r - c*r is not u in f32 once usage comes in bytes
+                used_before = used.clone()
+                qa_before = plan.queue_alloc[cp.queue_idx].clone()
             if cp.spread is not None:
                 g, skew = cp.spread
                 ref.spread_select_commit(
@@ -379,6 +385,9 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
                 job_flag[j] = flag
                 if int(flag) == 0:
                     revert(c, cp, flag, req, sl)
+                    idx = log_nodes[sl][:int(log_len[c])].long()
+                    used[idx] = used_before[idx]
+                    plan.queue_alloc[cp.queue_idx].copy_(qa_before)
         if not single:
             ref.finalize_job(job_placed[j], jp.occupied, jp.min_available,
                              class_placed[jp.class_begin:jp.class_end],
