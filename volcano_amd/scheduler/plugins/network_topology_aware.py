@@ -55,7 +55,7 @@ class NetworkTopologyAwarePlugin(Plugin):
                     vec += nt.resource_vector(ni.idle)
             free[hname] = vec
 
-        impossible_bit = nt.add_dynamic_bit("hn:none", [])
+        impossible_bit = nt.nowhere_bit()
         choice: Dict[str, Optional[str]] = {}
 
         def choose_domain(job) -> Optional[str]:

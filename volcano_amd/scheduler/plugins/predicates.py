@@ -19,6 +19,7 @@ from typing import Tuple
 
 import numpy as np
 
+from ..tensors import set_plane_bit
 from .base import Plugin, register
 
 
@@ -61,20 +62,41 @@ class PredicatesPlugin(Plugin):
         pod = t.pod
         tolerations = pod.tolerations if pod else []
         tolerated = nt.tolerated_mask(tolerations)
-        # register OR-set bits BEFORE the word arrays are sized so the
-        # widths line up
         extra_req, extra_forbid = self._affinity_bits(pod)
         extra_req = tuple(extra_req) + self._volume_zone_bits(pod)
-        require, forbid = nt.selector_bits(
+        req_bits, forbid_bits = nt.selector_bit_lists(
             pod.node_selector if pod else {}, pod.affinity if pod else None)
-        if extra_req or extra_forbid:
-            from ..tensors import set_plane_bit
-            for bit in extra_req:
+        if extra_req:
+            req_bits.extend(extra_req)
+        if extra_forbid:
+            forbid_bits.extend(extra_forbid)
+        # every bit above is registered, so the words are sized after it
+        if not hooks:
+            W = max(nt.labels.words, 1)
+            require = np.zeros(W, dtype=np.int64)
+            forbid = np.zeros(W, dtype=np.int64)
+            for bit in req_bits:
                 set_plane_bit(require, bit)
-            for bit in extra_forbid:
+            for bit in forbid_bits:
                 set_plane_bit(forbid, bit)
-        for hook in hooks:
-            hook(tclass, job, require, forbid)
+        else:
+            # Hooks set bits in place and may register new ones as they
+            # go: they work on vectors of the registry's full capacity (no
+            # bit it can hand out lies beyond), trimmed to the live width.
+            require = np.zeros(nt.labels.max_words, dtype=np.int64)
+            forbid = np.zeros(nt.labels.max_words, dtype=np.int64)
+            for bit in req_bits:
+                set_plane_bit(require, bit)
+            for bit in forbid_bits:
+                set_plane_bit(forbid, bit)
+            for hook in hooks:
+                hook(tclass, job, require, forbid)
+            W = max(nt.labels.words, 1)
+            require, forbid = require[:W].copy(), forbid[:W].copy()
+        # host-side readers (preempt) index the planes by these widths;
+        # only a class that opened a new word pays for the padding
+        if nt.planes_t is not None and len(require) > nt.planes_t.shape[0]:
+            nt.ensure_plane_width()
         out = (tolerated, require, forbid)
         if memoize:
             self._memo[key] = out
@@ -152,7 +174,7 @@ class PredicatesPlugin(Plugin):
 
         for k, vals in (aff.get("in") or {}).items():
             if len(vals) <= 1:
-                continue       # single-value handled by selector_bits
+                continue       # one value / none: selector_bits
             vset = set(vals)
             req.append(self._node_set_bit(
                 ("in", k, tuple(sorted(vals))),

@@ -36,9 +36,10 @@ _BLOCKING_EFFECTS = ("NoSchedule", "NoExecute")
 class BitRegistry:
     """Sticky mapping of string keys to bit positions across W int64 words."""
 
-    def __init__(self, max_words: int = 4):
+    def __init__(self, max_words: int = 4, what: str = "keys"):
         self.index: Dict[str, int] = {}
         self.max_words = max_words
+        self.what = what
 
     def bit(self, key: str) -> int:
         i = self.index.get(key)
@@ -46,7 +47,8 @@ class BitRegistry:
             i = len(self.index)
             if i >= self.max_words * 64:
                 raise OverflowError(
-                    f"bit registry overflow (> {self.max_words * 64} distinct keys)")
+                    f"bit registry overflow (> {self.max_words * 64} "
+                    f"distinct {self.what})")
             self.index[key] = i
         return i
 
@@ -66,8 +68,18 @@ def _set_bit(arr: np.ndarray, col: int, bit: int) -> None:
 
 
 def set_plane_bit(words: np.ndarray, bit: int) -> None:
-    """Set one bit in a [W] require/forbid word vector (int64-safe)."""
+    """Set one bit in a [W] require/forbid word vector (int64-safe), in
+    place.  Class-constraint hooks may call this with a bit they have only
+    just registered: ``PredicatesPlugin.class_constraints`` hands them
+    vectors of the registry's full capacity, so no bit lies beyond."""
     words[bit // 64] |= np.int64(_to_signed64(1 << (bit % 64)))
+
+
+# Label keys whose value is unique per node.  Spending a sticky static bit
+# on each pair would cap the cluster at the registry size (64 * label_words
+# nodes); such pairs resolve on demand instead, as a dynamic bit over the
+# nodes that carry them.
+PER_NODE_KEYS = frozenset({"kubernetes.io/hostname"})
 
 
 class NodeTensors:
@@ -77,8 +89,11 @@ class NodeTensors:
                  label_words: int = 16):
         self.dims = dims
         self.device = device
-        self.labels = BitRegistry(label_words)
-        self.taints = BitRegistry(1)
+        self.labels = BitRegistry(label_words, "label pairs")
+        self.taints = BitRegistry(1, "blocking taints")
+        self.per_node_keys = set(PER_NODE_KEYS)
+        # (key, value) -> node ids, for the per-node keys only (set by pack)
+        self.per_node_pairs: Dict[Tuple[str, str], List[int]] = {}
         self.names: List[str] = []
         self.index: Dict[str, int] = {}
         # torch views (created by pack)
@@ -124,25 +139,54 @@ class NodeTensors:
         node affinity ({"in": {k: [v...]}, "notIn": {k: [v...]}}).
 
         Reference: predicates plugin nodeaffinity filter
-        (plugins/predicates/predicates.go:34-47).  NOTE single-valued `in`
-        lists and `notIn` compile exactly; multi-valued `in` falls back to
-        requiring the first value only at pack level — callers with
-        multi-value affinity get the host-side slow path (Session keeps a
-        per-class candidate mask hook for that).
+        (plugins/predicates/predicates.go:34-47).  Single-valued `in`
+        lists and `notIn` compile here, and an `in` with no value at all
+        requires the shared all-zero ``nowhere`` bit (the upstream `In`
+        with an empty list matches no node).  Multi-valued `in` and the
+        other operators are node SETS, compiled by
+        ``PredicatesPlugin._affinity_bits``.
+
+        Every bit is registered before the words are sized: a pair that no
+        node carries takes a new bit, which may open a new word.
         """
-        W = max(self.labels.words, 1)
-        require = np.zeros(W, dtype=np.int64)
-        forbid = np.zeros(W, dtype=np.int64)
+        req_bits, forbid_bits = self.selector_bit_lists(selector, affinity)
+        return self.bit_words(req_bits), self.bit_words(forbid_bits)
+
+    def selector_bit_lists(self, selector: Dict[str, str],
+                           affinity: Optional[dict]
+                           ) -> Tuple[List[int], List[int]]:
+        """The (require, forbid) bits of ``selector_bits``, registered but
+        not yet packed into words."""
+        # per-node keys are rare: only they pay for the pair_bit call
+        per_node = self.per_node_keys
+        bit = self.labels.bit
+        req_bits, forbid_bits = [], []
         for k, v in (selector or {}).items():
-            _set_bit(require.reshape(W, 1), 0, self.label_bit(k, v))
+            req_bits.append(self.pair_bit(k, v) if k in per_node
+                            else bit(f"{k}={v}"))
         if affinity:
             for k, vals in (affinity.get("in") or {}).items():
                 if len(vals) == 1:
-                    _set_bit(require.reshape(W, 1), 0, self.label_bit(k, vals[0]))
+                    req_bits.append(self.pair_bit(k, vals[0]))
+                elif len(vals) == 0:
+                    req_bits.append(self.nowhere_bit())
             for k, vals in (affinity.get("notIn") or {}).items():
                 for v in vals:
-                    _set_bit(forbid.reshape(W, 1), 0, self.label_bit(k, v))
-        return require, forbid
+                    forbid_bits.append(self.pair_bit(k, v))
+        return req_bits, forbid_bits
+
+    def pair_bit(self, key: str, value: str) -> int:
+        """The plane bit that is set exactly on the nodes labelled
+        ``key=value``: the static pair bit, or for a per-node key a dynamic
+        bit over the nodes of the last pack that carry the pair."""
+        if key in self.per_node_keys:
+            return self.add_dynamic_bit(
+                f"pn:{key}={value}", self.per_node_pairs.get((key, value), ()))
+        return self.label_bit(key, value)
+
+    def nowhere_bit(self) -> int:
+        """A dynamic bit no node carries: requiring it is unsatisfiable."""
+        return self.add_dynamic_bit("nowhere", ())
 
     # -- packing -------------------------------------------------------------
     def pack_dynamic(self, nodes: List[NodeInfo], ledger=None) -> bool:
@@ -207,15 +251,23 @@ class NodeTensors:
         N = len(nodes)
 
         # first walk fixes the dim count and assigns any unseen label/taint
-        # bits so R and W are final before arrays are sized
-        for ni in nodes:
+        # bits so R and W are final before arrays are sized.  Per-node keys
+        # take no static bit: their pairs are kept as node-id lists and
+        # resolve through pair_bit when a class names one.
+        per_node = self.per_node_keys
+        pairs: Dict[Tuple[str, str], List[int]] = {}
+        for i, ni in enumerate(nodes):
             for k in ni.allocatable.q:
                 self.dims.add(k)
             for t in ni.node.taints:
                 if t.effect in _BLOCKING_EFFECTS:
                     self.taint_bit(t)
             for k, v in ni.node.meta.labels.items():
-                self.label_bit(k, v)
+                if k in per_node:
+                    pairs.setdefault((k, v), []).append(i)
+                else:
+                    self.label_bit(k, v)
+        self.per_node_pairs = pairs
         R = self.r
         W = self.labels.words
 
@@ -267,7 +319,8 @@ class NodeTensors:
                 if t.effect in _BLOCKING_EFFECTS:
                     taints[i] |= np.int64(_to_signed64(1 << self.taint_bit(t)))
             for k, v in ni.node.meta.labels.items():
-                _set_bit(planes, i, self.label_bit(k, v))
+                if k not in per_node:
+                    _set_bit(planes, i, self.label_bit(k, v))
 
         dev = self.device
         # numpy mirrors for host-side rare paths (preempt/reclaim scans) —
