@@ -110,7 +110,10 @@ def log_of(seq: List[int]):
 
 def base_case(name, N, D, R, seed, mode, *, ntasks=None, count=None,
               unlabeled=0.1, infeasible=0.15, cap_hi=4, cap_lo=0,
-              identity=False, quota=None, fuse_min=-1) -> AffinityCase:
+              identity=False, quota=None, fuse_min=-1,
+              scores=None) -> AffinityCase:
+    """``scores``: a function ``(N, rng) -> float32[N]`` that replaces the
+    four-valued draw (the infeasible share is still set to -inf here)."""
     rng = np.random.RandomState(seed)
     D = min(D, N)
     if identity:
@@ -122,6 +125,9 @@ def base_case(name, N, D, R, seed, mode, *, ntasks=None, count=None,
         if N > 1:
             dom_of[rng.rand(N) < unlabeled] = -1
     score = (rng.randint(0, 4, size=N) * 0.25).astype(np.float32)
+    if scores is not None:
+        score = np.array(scores(N, rng), dtype=np.float32)
+        assert score.shape == (N,)
     if N > 1:
         score[rng.rand(N) < infeasible] = NEG_INF
     cap = rng.randint(cap_lo, cap_hi + 1, size=N).astype(np.int32)
@@ -387,8 +393,12 @@ class AffinityPlanCase:
     roles: dict                    # name -> class index
 
 
-def affinity_plan_case(N=1500, R=5, W=1, seed=33) -> AffinityPlanCase:
-    """Group 0: zones (3 domains, empty at the start), shared by affinity
+def affinity_plan_case(N=1500, R=5, W=1, seed=33, inexact=False,
+                       bias_shift=0.0) -> AffinityPlanCase:
+    """``inexact``: the inexact node state and bias rows, ``w_bal`` 1 for
+    every class; ``bias_shift`` is added to the plan-wide bias.
+
+    Group 0: zones (3 domains, empty at the start), shared by affinity
     classes.  Group 1: zones of a spread rule.  Group 2: racks of an anti
     rule (7 domains, two occupied).  Group 3: per-node affinity (identity).
 
@@ -403,7 +413,9 @@ def affinity_plan_case(N=1500, R=5, W=1, seed=33) -> AffinityPlanCase:
     affinity job of group 3 · 6 plain jobs."""
     import _kernel_cases as kc
     rng = np.random.RandomState(seed)
-    st = kc.dyadic_state(N, R, W, seed)
+    st = kc.dyadic_state(N, R, W, seed, inexact=inexact)
+    if bias_shift:
+        st["bias"] = st["bias"] + np.float32(bias_shift)
     classes, jobs, spread, affinity, roles = [], [], {}, {}, {}
 
     def add_job(cls, occupied, min_avail):
@@ -456,14 +468,16 @@ def affinity_plan_case(N=1500, R=5, W=1, seed=33) -> AffinityPlanCase:
               (np.arange(N, dtype=np.int32), np.zeros(N, dtype=np.int32))]
     ql, qa = kc._queues(rng, R, limit_dim0=30)
     base = kc.PlanCase("affinity", N, R, W, st, classes, jobs, ql, qa,
-                       kc._bias_rows(rng, N, 2))
+                       kc._bias_rows(rng, N, 2, inexact=inexact),
+                       w_bal=1.0 if inexact else 0.0)
     return AffinityPlanCase(base, spread, affinity, groups, roles)
 
 
-def build_affinity_plan(case: AffinityPlanCase, device, *, rules=True):
+def build_affinity_plan(case: AffinityPlanCase, device, *, rules=True,
+                        w_bal: float = 0.0):
     """``rules=False``: the same classes with no domain rule at all."""
     import _kernel_cases as kc
-    plan = kc.build_plan(case.base, device)
+    plan = kc.build_plan(case.base, device, w_bal)
     if not rules:
         return plan
     for dom_of, count in case.groups:

@@ -102,7 +102,10 @@ def log_of(seq: List[int]):
 
 def random_case(name, N, D, skew, R, seed, *, ntasks=None, quota=None,
                 unlabeled=0.1, infeasible=0.15, dead_domain=False,
-                unbalanced=False, cap_hi=4, fuse_min=-1) -> SpreadCase:
+                unbalanced=False, cap_hi=4, fuse_min=-1,
+                scores=None) -> SpreadCase:
+    """``scores``: a function ``(N, rng) -> float32[N]`` that replaces the
+    four-valued draw (the infeasible share is still set to -inf here)."""
     rng = np.random.RandomState(seed)
     D = min(D, N)
     # every domain owns at least one node when N allows it
@@ -111,6 +114,9 @@ def random_case(name, N, D, skew, R, seed, *, ntasks=None, quota=None,
     if N > 1:
         dom_of[rng.rand(N) < unlabeled] = -1
     score = (rng.randint(0, 4, size=N) * 0.25).astype(np.float32)
+    if scores is not None:
+        score = np.array(scores(N, rng), dtype=np.float32)
+        assert score.shape == (N,)
     score[rng.rand(N) < infeasible] = NEG_INF
     cap = rng.randint(0, cap_hi + 1, size=N).astype(np.int32)
     if dead_domain and D > 1:
@@ -148,8 +154,12 @@ class SpreadPlanCase:
     roles: dict                    # name -> class index
 
 
-def spread_plan_case(N=1000, R=5, W=1, seed=21, bulk=True) -> SpreadPlanCase:
-    """Job order: [one 600-task plain class] · a two-role gang whose first
+def spread_plan_case(N=1000, R=5, W=1, seed=21, bulk=True, inexact=False,
+                     bias_shift=0.0) -> SpreadPlanCase:
+    """``inexact``: the inexact node state and bias rows, ``w_bal`` 1 for
+    every class; ``bias_shift`` is added to the plan-wide bias.
+
+    Job order: [one 600-task plain class] · a two-role gang whose first
     role spreads over group 0 and whose second role misses its minimum
     (the job reverts) · 36 small plain single-class jobs (a chain run) · a
     spread job of group 0 (must see the restored counts) · a spread job
@@ -157,7 +167,9 @@ def spread_plan_case(N=1000, R=5, W=1, seed=21, bulk=True) -> SpreadPlanCase:
     and reverts in the select · a spread job of group 1 · 8 plain jobs."""
     import _kernel_cases as kc
     rng = np.random.RandomState(seed)
-    st = kc.dyadic_state(N, R, W, seed)
+    st = kc.dyadic_state(N, R, W, seed, inexact=inexact)
+    if bias_shift:
+        st["bias"] = st["bias"] + np.float32(bias_shift)
     classes, jobs, spread, roles = [], [], {}, {}
 
     def add_job(cls, occupied, min_avail):
@@ -202,13 +214,14 @@ def spread_plan_case(N=1000, R=5, W=1, seed=21, bulk=True) -> SpreadPlanCase:
                (rng.rand(N) < 0.3).astype(np.int32))]
     ql, qa = kc._queues(rng, R, limit_dim0=30)
     base = kc.PlanCase("spread", N, R, W, st, classes, jobs, ql, qa,
-                       kc._bias_rows(rng, N, 2))
+                       kc._bias_rows(rng, N, 2, inexact=inexact),
+                       w_bal=1.0 if inexact else 0.0)
     return SpreadPlanCase(base, spread, groups, roles)
 
 
-def build_spread_plan(case: SpreadPlanCase, device):
+def build_spread_plan(case: SpreadPlanCase, device, w_bal: float = 0.0):
     import _kernel_cases as kc
-    plan = kc.build_plan(case.base, device)
+    plan = kc.build_plan(case.base, device, w_bal)
     for dom_of, count in case.groups:
         plan.add_spread_group(dom_of.copy(), count.copy())
     for c, sp in case.spread.items():
