@@ -4,8 +4,11 @@ whole-framework-on-hardware test the round-end driver replays."""
 
 import random
 
+import numpy as np
 import pytest
 import torch
+
+import _coherence_cases as cc
 
 pytestmark = pytest.mark.gpu
 
@@ -39,6 +42,8 @@ def test_gpu_full_stack_churn():
     kubelet = FakeKubelet(store)
 
     submitted = 0
+    checked = 0
+    placed_by_cycle = []
     for cycle in range(12):
         for _ in range(10):          # 10 new gangs per cycle
             submitted += 1
@@ -47,7 +52,19 @@ def test_gpu_full_stack_churn():
                 cpu=str(rng.choice([1, 2, 4])),
                 ttl_seconds_after_finished=0.0))
         cm.sync_until_quiet()
-        sched.run_once()
+        ssn = sched.run_once()
+        # what the cycle left on the device, before anything re-packs it:
+        # every dim of every node against the per-task truth.  Whole cores
+        # and whole GiB, so equality.
+        nt = cache.node_tensors
+        left = nt.used_t.cpu().double().numpy().T
+        truth, _ = cc.host_truth(cache, ssn)
+        assert left.shape == truth.shape
+        assert np.array_equal(left, truth), \
+            f"cycle {cycle}: used_t != per-task truth at " \
+            f"{np.argwhere(left != truth)[:4].tolist()}"
+        checked += 1
+        placed_by_cycle.append(float(truth.sum()))
         kubelet.tick()
         if cycle % 2 == 1:
             running = [j for j in store.list("Job")
@@ -60,6 +77,9 @@ def test_gpu_full_stack_churn():
         cm.sync_until_quiet()
 
     torch.cuda.synchronize()
+    assert checked == 12
+    # the per-cycle comparison saw usage, and usage that moved
+    assert min(placed_by_cycle) > 0 and len(set(placed_by_cycle)) > 1
     # invariants after 12 churn cycles on the HIP path
     bound = sum(1 for p in store.list("Pod") if p.node_name)
     assert bound > 0
@@ -68,7 +88,9 @@ def test_gpu_full_stack_churn():
                          if t.status.occupies_node)
         assert abs(recomputed - ni.used.get(CPU)) < 1.0
         assert ni.used.get(CPU) <= ni.allocatable.get(CPU) + 1.0
-    # device tensors agree with the host mirror
+    # device tensors agree with the host mirror.  ensure_packed() copies
+    # the mirror onto the device first, so this only checks the pack; the
+    # state a cycle leaves behind is compared inside the loop above.
     cache.ensure_packed()
     nt = cache.node_tensors
     cpu_idx = nt.dims.index[CPU]
