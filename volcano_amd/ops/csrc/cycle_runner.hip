@@ -19,6 +19,7 @@ namespace {
 
 const int CHAIN_MIN = 32;     // shortest run of jobs worth a chain
 const int BULK_TASKS = 512;   // classes this large take the bulk select
+const int MODE_HYPERNODE = 3; // class_mode of a network-topology class
 
 // The opt-in paths, read once per cycle so tests can flip them.
 //
@@ -136,7 +137,8 @@ struct Runner {
             v.mode = cy.class_mode != nullptr ? cy.class_mode[c] : 0;
             if (v.mode == 0) v.skew = cy.class_skew[c];
             v.D = cy.domains[g];
-            v.dom_of = cy.dom_of + (size_t)g * cy.N;
+            const int row = cy.group_row != nullptr ? cy.group_row[g] : g;
+            v.dom_of = cy.dom_of + (size_t)row * cy.N;
             v.dom_count = cy.count + cy.count_off[g];
         }
         return v;
@@ -189,7 +191,8 @@ struct Runner {
     }
 
     void revert(const ClassView& v) const {
-        if (v.group >= 0) {
+        // a network-topology class holds a table, not counts: plain revert
+        if (v.group >= 0 && v.mode != MODE_HYPERNODE) {
             vamd_spread_revert(v.job_flag, v.log_nodes, v.log_counts,
                                v.log_len, v.req, cy.used, v.queue_alloc,
                                v.placed, v.job_placed, v.dom_of, v.dom_count,
@@ -202,7 +205,14 @@ struct Runner {
     }
 
     void run_class(const ClassView& v) const {
-        if (v.group >= 0 && v.mode != 0) {
+        if (v.group >= 0 && v.mode == MODE_HYPERNODE) {
+            // network topology: the mask confines the class to the one
+            // hypernode chosen from the live cap; the group's slice is a
+            // read-only table, so no count update follows
+            score(v);
+            domain_mask(v);
+            select(v);
+        } else if (v.group >= 0 && v.mode != 0) {
             // inter-pod affinity / keyed anti-affinity: the rule collapses
             // into a mask over score/cap computed from the group's live
             // counts, then the ordinary select (bulk by size) and one

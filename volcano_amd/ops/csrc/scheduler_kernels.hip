@@ -1101,6 +1101,232 @@ domain_mask_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------
+// Network-topology domain choice (mode 3 of vamd_domain_mask) — oracle:
+// reference.py hypernode_mask.  A gang is confined to ONE hypernode of the
+// lowest tier that can hold `need` instances, judged by the live per-node
+// cap of score_cap (so fragmentation, taints, selectors and everything
+// placed earlier in the cycle count), tightest fit within the tier.
+//
+// The host numbers the leaves depth-first, so a hypernode of ANY tier is
+// one contiguous leaf range [lo, hi): one pass over the nodes yields the
+// per-leaf sums, one exclusive scan turns them into P[0..D], and the
+// capacity of any domain is P[hi] - P[lo].  Four phases, one launch:
+//
+//   a. leaf sums.  A wave reads 64 consecutive nodes; lanes holding the
+//      same leaf as their left neighbour form a run (racks are usually
+//      consecutive in index).  Run heads come from one ballot, a segmented
+//      shuffle reduce brings each run's sum to its head lane, and only the
+//      heads issue an atomic: one per run instead of one per node.
+//   b. chunked exclusive scan over D+1 int64 (contiguous chunk per thread,
+//      __shfl_up wave scan, wave partials through LDS), in place.
+//   c. tier search: threads stride the tier's (lo, hi) pairs, one block
+//      min-reduce over (capacity, table index) — ties to the lower index —
+//      thread 0 publishes winner and found flag together, the tier loop
+//      exits block-uniformly after the barrier.
+//   d. mask pass: nodes outside the winner's range get score = -inf,
+//      cap = 0 (unlabelled nodes included); kept nodes are untouched.  No
+//      winner: hard masks every node, soft none.
+//
+// Sums are int64 throughout (a cap can be 2^31 - 1).  They live in LDS
+// while D <= HN_LDS_LEAVES — 8*(D+1) <= 32 KB, a fifth of the 160 KB of a
+// gfx950 CU, beside ~400 B of reduce partials — and in `gsum` (global,
+// 8*(D+1) bytes) above that; the choice, T and soft are block-uniform, so
+// every barrier is reached by the whole block.  Table entries are bounds-
+// checked: a pair outside 0 <= lo <= hi <= D never wins.
+// ---------------------------------------------------------------------------
+#define DM_HYPERNODE 3
+#define HN_LDS_LEAVES 4095
+#define HN_TAB_HEAD 5
+
+struct CapIdx { long long c; int i; };
+
+DEVINL CapIdx tighter(CapIdx a, CapIdx b) {
+    if (b.c < a.c || (b.c == a.c && b.i < a.i)) return b;
+    return a;
+}
+
+DEVINL CapIdx wave_min_cap(CapIdx x, int width) {
+    for (int off = width / 2; off > 0; off >>= 1) {
+        CapIdx o;
+        o.c = __shfl_down(x.c, off);
+        o.i = __shfl_down(x.i, off);
+        x = tighter(x, o);
+    }
+    return x;
+}
+
+// Leaf sums in global memory are produced by device-scope atomics, which
+// execute at the L2: read them back with loads of the same scope.
+template <bool IN_LDS>
+DEVINL long long hn_load(const long long* P, int d) {
+    if (IN_LDS) return P[d];
+    return __hip_atomic_load(P + d, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <bool IN_LDS>
+DEVINL void hn_store(long long* P, int d, long long v) {
+    if (IN_LDS) P[d] = v;
+    else __hip_atomic_store(P + d, v, __ATOMIC_RELAXED,
+                            __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <bool IN_LDS>
+DEVINL void hypernode_mask_body(
+    float* __restrict__ score, int* __restrict__ cap,
+    const int* __restrict__ leaf_of, const int* __restrict__ tab,
+    int D, long long* P, int N,
+    long long* s_wsum, CapIdx* s_wmin, int* s_pub)
+{
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wid = tid / WAVE;
+    const int M = D + 1;
+
+    for (int d = tid; d < M; d += SP_THREADS) hn_store<IN_LDS>(P, d, 0ll);
+    __syncthreads();
+
+    // a. leaf sums: whole waves walk 64 consecutive nodes, so the trip
+    // count is wave-uniform and every shuffle sees all 64 lanes
+    for (int base = wid * WAVE; base < N; base += SP_THREADS) {
+        const int i = base + lane;
+        int leaf = -1;
+        long long c = 0ll;
+        if (i < N) {
+            leaf = leaf_of[i];
+            if (leaf >= 0 && leaf < D) c = (long long)cap[i];
+            else leaf = -1;
+        }
+        const int left = __shfl_up(leaf, 1);
+        const bool is_head = lane == 0 || left != leaf;
+        const uint64_t heads = __ballot(is_head);
+        // first head to the right of this lane closes its run
+        const uint64_t after = lane < WAVE - 1 ? heads >> (lane + 1) : 0ull;
+        const int end = after ? lane + 1 + (__ffsll((long long)after) - 1)
+                              : WAVE;
+        for (int off = 1; off < WAVE; off <<= 1) {
+            const long long o = __shfl_down(c, off);
+            if (lane + off < end) c += o;
+        }
+        if (is_head && leaf >= 0 && c != 0ll) {
+            if (IN_LDS)
+                __hip_atomic_fetch_add(P + leaf, c, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_WORKGROUP);
+            else
+                __hip_atomic_fetch_add(P + leaf, c, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    __syncthreads();
+
+    // b. exclusive scan of P[0..D] in place; P[D] entered as 0
+    {
+        const int chunk = (M + SP_THREADS - 1) / SP_THREADS;
+        const int lo = min(tid * chunk, M);
+        const int hi = min(lo + chunk, M);
+        long long own = 0ll;
+        for (int d = lo; d < hi; ++d) own += hn_load<IN_LDS>(P, d);
+        long long v = own;
+        for (int off = 1; off < WAVE; off <<= 1) {
+            const long long o = __shfl_up(v, off);
+            if (lane >= off) v += o;
+        }
+        if (lane == WAVE - 1) s_wsum[wid] = v;
+        __syncthreads();
+        if (wid == 0) {
+            long long w = lane < SP_WAVES ? s_wsum[lane] : 0ll;
+            for (int off = 1; off < SP_WAVES; off <<= 1) {
+                const long long o = __shfl_up(w, off);
+                if (lane >= off) w += o;
+            }
+            if (lane < SP_WAVES) s_wsum[lane] = w;
+        }
+        __syncthreads();
+        long long run = v - own + (wid > 0 ? s_wsum[wid - 1] : 0ll);
+        for (int d = lo; d < hi; ++d) {
+            const long long l = hn_load<IN_LDS>(P, d);
+            hn_store<IN_LDS>(P, d, run);
+            run += l;
+        }
+    }
+    if (tid == 0) { s_pub[0] = 0; s_pub[1] = 0; s_pub[2] = 0; }
+    __syncthreads();
+
+    // c. tier search, lowest tier first
+    const int T = tab[0];
+    const long long need = (long long)tab[1];
+    const int pin_lo = tab[2];
+    const int pin_hi = tab[3];
+    const bool soft = tab[4] != 0;
+    for (int t = 0; t < T; ++t) {
+        const int o0 = tab[HN_TAB_HEAD + t];
+        const int npair = (tab[HN_TAB_HEAD + t + 1] - o0) / 2;
+        CapIdx loc; loc.c = INT64_MAX; loc.i = INT32_MAX;
+        for (int k = tid; k < npair; k += SP_THREADS) {
+            const int lo = tab[o0 + 2 * k];
+            const int hi = tab[o0 + 2 * k + 1];
+            if (lo < 0 || hi < lo || hi > D) continue;
+            if (lo > pin_lo || pin_hi > hi) continue;
+            CapIdx c; c.i = k;
+            c.c = hn_load<IN_LDS>(P, hi) - hn_load<IN_LDS>(P, lo);
+            if (c.c >= need) loc = tighter(loc, c);
+        }
+        loc = wave_min_cap(loc, WAVE);
+        if (lane == 0) s_wmin[wid] = loc;
+        __syncthreads();
+        if (wid == 0) {
+            CapIdx b; b.c = INT64_MAX; b.i = INT32_MAX;
+            if (lane < SP_WAVES) b = s_wmin[lane];
+            b = wave_min_cap(b, SP_WAVES);
+            // thread 0 owns the published words
+            if (lane == 0 && b.i != INT32_MAX) {
+                s_pub[1] = tab[o0 + 2 * b.i];
+                s_pub[2] = tab[o0 + 2 * b.i + 1];
+                s_pub[0] = 1;
+            }
+        }
+        __syncthreads();
+        if (s_pub[0]) break;         // block-uniform
+    }
+
+    // d. mask pass
+    const bool found = s_pub[0] != 0;
+    if (!found && soft) return;
+    const int win_lo = s_pub[1];
+    const int win_hi = found ? s_pub[2] : 0;      // hard, no winner: empty
+    for (int i = tid; i < N; i += SP_THREADS) {
+        const int leaf = leaf_of[i];
+        if (leaf < win_lo || leaf >= win_hi) {
+            score[i] = NEG_INF;
+            cap[i] = 0;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(SP_THREADS)
+hypernode_mask_kernel(
+    float* __restrict__ score,            // [N] in place
+    int* __restrict__ cap,                // [N] in place
+    const int* __restrict__ leaf_of,      // [N] leaf id, -1 = in no hypernode
+    const int* __restrict__ tab,          // the group's table (vamd_api.h)
+    int D,
+    long long* __restrict__ gsum,         // [D+1] scratch, D > HN_LDS_LEAVES
+    int N)
+{
+    __shared__ long long s_leaf[HN_LDS_LEAVES + 1];
+    __shared__ long long s_wsum[SP_WAVES];
+    __shared__ CapIdx s_wmin[SP_WAVES];
+    __shared__ int s_pub[3];              // found, winner lo, winner hi
+
+    if (D <= HN_LDS_LEAVES)               // launch argument: block-uniform
+        hypernode_mask_body<true>(score, cap, leaf_of, tab, D, s_leaf, N,
+                                  s_wsum, s_wmin, s_pub);
+    else
+        hypernode_mask_body<false>(score, cap, leaf_of, tab, D, gsum, N,
+                                   s_wsum, s_wmin, s_pub);
+}
+
 // After the select of an affinity / anti-affinity class: the logged
 // placements join the group's per-domain counts.  Integer atomics — log
 // entries can share a domain.  A fused gang revert leaves zeroed counts in
@@ -1662,10 +1888,19 @@ void vamd_domain_mask(
     float* score, int* cap, const int* dom_of, const int* dom_count, int D,
     int mode, void* scratch, int N, hipStream_t stream)
 {
+    if (mode == DM_HYPERNODE) {
+        // dom_of = leaf_of, dom_count = the group's table, D = leaves
+        hipLaunchKernelGGL(vamd::hypernode_mask_kernel, dim3(1),
+                           dim3(SP_THREADS), 0, stream, score, cap, dom_of,
+                           dom_count, D, (long long*)scratch, N);
+        return;
+    }
     hipLaunchKernelGGL(vamd::domain_mask_kernel, dim3(1), dim3(SP_THREADS),
                        0, stream, score, cap, dom_of, dom_count, D, mode,
                        (unsigned long long*)scratch, N);
 }
+
+int vamd_hypernode_lds_leaves(void) { return HN_LDS_LEAVES; }
 
 void vamd_domain_count_add(
     const int* log_nodes, const int* log_counts, const int* log_len,

@@ -73,9 +73,31 @@ void vamd_spread_revert(
 //     count == 0, with cap 1.
 // Nodes with dom_of < 0 are masked in both modes.  `scratch` holds 8*D
 // bytes, 8-byte aligned (used in mode 2).  D in [1, N].
+//   mode 3, network topology: confine the class to ONE hypernode, chosen
+//     from the live cap.  dom_of = leaf_of[N] (the node's leaf id in
+//     [0, D), -1 = in no hypernode; leaves are numbered depth-first, so a
+//     hypernode of any tier is one leaf range [lo, hi)), D = number of
+//     leaves, and dom_count is a read-only int32 table instead of counts:
+//       tab[0] T       tiers to try, lowest first (>= 1)
+//       tab[1] need    instances that must fit in the domain (>= 1)
+//       tab[2] pin_lo  a domain is eligible iff lo <= pin_lo and
+//       tab[3] pin_hi    pin_hi <= hi; no pin: pin_lo = D, pin_hi = 0
+//       tab[4] soft    0 = hard, 1 = soft
+//       tab[5..5+T]    off[t]: start of tier t's (lo, hi) pairs, off[T] =
+//                      end; offsets into tab
+//       ...            the pairs, tier by tier
+//     With C = sum of cap over the leaves of [lo, hi) (int64), the first
+//     tier with an eligible domain of C >= need wins, within it the
+//     smallest C, ties to the lower table index.  Nodes outside the
+//     winner are masked; without a winner hard masks every node, soft
+//     none.  `scratch` holds 8*(D+1) bytes (used above
+//     vamd_hypernode_lds_leaves() leaves).
 void vamd_domain_mask(
     float* score, int* cap, const int* dom_of, const int* dom_count, int D,
     int mode, void* scratch, int N, hipStream_t stream);
+
+// Largest D whose leaf sums mode 3 keeps in LDS.
+int vamd_hypernode_lds_leaves(void);
 
 // dom_count[dom_of[log_nodes[e]]] += log_counts[e] for e < *log_len
 // (<= K), after the select of a domain-mask class.
@@ -175,16 +197,18 @@ struct VamdCycle {
     int* job_placed;               // [J]
     uint8_t* job_flag;             // [J]
     unsigned* sort_scratch;        // [4N] bulk-select radix scratch (nullable)
-    // domain-rule block (topology spread, inter-pod (anti-)affinity): live
-    // only when class_group, dom_of, count and domain_scratch are all set
+    // domain-rule block (topology spread, inter-pod (anti-)affinity,
+    // network topology): live only when class_group, dom_of, count and
+    // domain_scratch are all set
     const int32_t* class_group;    // HOST [C]: group index or -1
     const int32_t* class_skew;     // HOST [C]: maxSkew (>= 1, mode 0)
-    const int32_t* class_mode;     // HOST [C]: 0 / 1 / 2; null = all 0
-    const int32_t* dom_of;         // [G, N]
-    int32_t* count;                // groups back to back
+    const int32_t* class_mode;     // HOST [C]: 0 / 1 / 2 / 3; null = all 0
+    const int32_t* dom_of;         // [rows, N]; rows = G without group_row
+    int32_t* count;                // groups back to back (mode 3: tables)
     const int32_t* count_off;      // HOST [G]: offset into count
     const int32_t* domains;        // HOST [G]: D of each group
     void* domain_scratch;          // 12*N bytes, 8-aligned
+    const int32_t* group_row;      // HOST [G]: row of dom_of for group g; null = g
 };
 
 // Device copies of the descriptor arrays (chain and megacycle paths).
@@ -227,6 +251,11 @@ void vamd_megacycle(const VamdCycle& cy, const VamdDevDescs& dd,
 //     runs vamd_score_cap -> vamd_domain_mask -> vamd_select_commit (bulk
 //     by size, given sort_scratch) -> vamd_domain_count_add: a launch
 //     count constant in ntasks; it reverts through vamd_spread_revert.
+//   * A network-topology class (mode 3) always runs vamd_score_cap ->
+//     vamd_domain_mask(3) -> vamd_select_commit (bulk by size): its count
+//     slice is a read-only table, so there is no count update and it
+//     reverts through vamd_cond_revert.  All such groups of a cycle can
+//     share one leaf_of row through group_row.
 //   * With the domain block dead (or every group -1) nothing above
 //     changes a single launch.
 // Returns 0; nonzero, before any HIP call, when cy->struct_size is not

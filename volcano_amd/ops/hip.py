@@ -16,8 +16,14 @@ from typing import Optional
 import torch
 
 from .build import LIB_PATH, build
+from .reference import check_hypernode_table
 
 _lib = None
+
+# Largest leaf count whose sums mode 3 of ``domain_mask`` keeps in LDS
+# (``HN_LDS_LEAVES`` in scheduler_kernels.hip; checked against the library
+# on load).  Above it the sums live in the scratch buffer.
+HYPERNODE_LDS_LEAVES = 4095
 
 
 class VamdClassDesc(Structure):
@@ -51,7 +57,7 @@ class VamdCycle(Structure):
         "score_scratch", "cap_scratch", "log_nodes", "log_counts", "log_len",
         "class_placed", "job_placed", "job_flag", "sort_scratch",
         "class_group", "class_skew", "class_mode", "dom_of", "count",
-        "count_off", "domains", "domain_scratch")]
+        "count_off", "domains", "domain_scratch", "group_row")]
 
 
 def _load():
@@ -79,6 +85,11 @@ def _load():
     lib.vamd_spread_revert.restype = None
     lib.vamd_domain_mask.restype = None
     lib.vamd_domain_count_add.restype = None
+    lib.vamd_hypernode_lds_leaves.restype = c_int
+    if lib.vamd_hypernode_lds_leaves() != HYPERNODE_LDS_LEAVES:
+        raise RuntimeError(
+            "the loaded kernel library and this module disagree on "
+            "HYPERNODE_LDS_LEAVES; rebuild (python -m volcano_amd.ops.build)")
     _lib = lib
     return lib
 
@@ -222,6 +233,43 @@ def domain_mask(score, cap, dom_of, dom_count, mode, scratch=None):
         c_int(int(mode)), _p(scratch), c_int(N), _stream())
 
 
+def hypernode_mask(score, cap, leaf_of, table, n_leaves, scratch=None,
+                   check=True):
+    """Network-topology domain choice (mode 3 of the domain mask; after
+    score_cap, before select_commit): keeps the nodes of the one hypernode
+    the ``table`` rule picks from the live ``cap`` (layout in
+    ``vamd_api.h``; built by ``reference.hypernode_table``), masks the
+    rest.  ``score`` and ``cap`` are changed in place.
+
+    The kernel trusts the table's offsets, so ``check`` (default) copies
+    the table to the host and validates it first — a device-to-host copy
+    and a sync.  A caller that validated its table on the host
+    (``reference.check_hypernode_table``; plan building does) passes
+    ``check=False`` and gets a plain asynchronous launch."""
+    lib = _load()
+    N = score.shape[0]
+    D = int(n_leaves)
+    if not 1 <= D <= max(N, 1):
+        raise ValueError(f"hypernode_mask: D={D} outside [1, N={N}]")
+    if leaf_of.shape[0] != N or cap.shape[0] != N:
+        raise ValueError("hypernode_mask: leaf_of and cap must have one "
+                         "entry per node")
+    if leaf_of.dtype != torch.int32 or table.dtype != torch.int32 \
+            or cap.dtype != torch.int32 or score.dtype != torch.float32:
+        raise ValueError("hypernode_mask: score is float32; cap, leaf_of "
+                         "and table are int32")
+    if check:
+        check_hypernode_table(table.cpu().numpy(), D)
+    if scratch is None:
+        scratch = spread_scratch(N, score.device)
+    elif scratch.numel() * scratch.element_size() < 8 * (D + 1):
+        raise ValueError("hypernode_mask: scratch smaller than 8*(D+1) "
+                         "bytes")
+    lib.vamd_domain_mask(
+        _p(score), _p(cap), _p(leaf_of), _p(table), c_int(D), c_int(3),
+        _p(scratch), c_int(N), _stream())
+
+
 def domain_count_add(log_nodes, log_counts, log_len, dom_of, dom_count):
     """The logged placements of a domain-mask class join the group's
     per-domain counts (after select_commit)."""
@@ -290,8 +338,12 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
     i32 [G, N], ``count`` device i32 (groups back to back), ``count_off``/
     ``domains`` host int32 numpy [G], ``scratch`` device
     (``spread_scratch``).  An optional ``class_mode`` (host int32 numpy
-    [C]: 0 spread, 1 inter-pod affinity, 2 keyed anti-affinity) fills the
-    mode column; without it every class of a group is a spread class."""
+    [C]: 0 spread, 1 inter-pod affinity, 2 keyed anti-affinity, 3 network
+    topology) fills the mode column; without it every class of a group is
+    a spread class.  An optional ``group_row`` (host int32 numpy [G]) names
+    the row of ``dom_of`` each group reads — all network-topology groups
+    share one ``leaf_of`` row; without it group g reads row g.  The
+    ``count`` slice of a mode-3 group is its table."""
     lib = _load()
     R, N = alloc_t.shape
     cy = VamdCycle(
@@ -324,6 +376,12 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
         cy.count_off = spread["count_off"].ctypes.data
         cy.domains = spread["domains"].ctypes.data
         cy.domain_scratch = _addr(spread["scratch"])
+        rows = spread.get("group_row")
+        if rows is not None:
+            if rows.dtype != "int32" or \
+                    rows.shape[0] != spread["domains"].shape[0]:
+                raise ValueError("run_cycle: group_row must be int32 [G]")
+            cy.group_row = rows.ctypes.data
     rc = lib.vamd_run_cycle(ctypes.byref(cy), _stream())
     if rc != 0:
         raise RuntimeError(

@@ -22,6 +22,8 @@ Kernel inventory (SURVEY.md §2.9 K1–K6 mapping):
   topology-spread bound checked before every placement, and its rollback.
 * ``affinity_select_commit`` — K2 select under an inter-pod (anti-)affinity
   domain rule checked before every placement (reverts: ``spread_revert``).
+* ``hypernode_mask`` — network-topology domain choice from the live cap:
+  a mask before ``select_commit`` (reverts: ``cond_revert``).
 * ``drf_share``      — K3 dominant share per job.
 * ``waterfill``      — K3 proportion/capacity deserved water-filling.
 
@@ -415,6 +417,117 @@ def affinity_select_commit(
     queue_alloc += torch.tensor(float(total), device=dev) * req
     placed.fill_(total)
     job_placed.add_(total)
+
+
+HYPERNODE = 3                   # domain-rule mode of hypernode_mask
+HN_TAB_HEAD = 5                 # T, need, pin_lo, pin_hi, soft
+
+
+def hypernode_table(tiers, need: int, n_leaves: int, pin=None,
+                    soft: bool = False):
+    """The int32 table of one network-topology group (layout in
+    ``vamd_api.h``): ``tiers`` is a list, lowest tier first, of lists of
+    ``(lo, hi)`` leaf ranges; ``pin`` a leaf range every candidate must
+    contain, or None."""
+    import numpy as np
+    T = len(tiers)
+    pin_lo, pin_hi = (n_leaves, 0) if pin is None else pin
+    head = [T, int(need), int(pin_lo), int(pin_hi), 1 if soft else 0]
+    off = HN_TAB_HEAD + T + 1
+    offs, pairs = [], []
+    for tier in tiers:
+        offs.append(off + len(pairs))
+        for lo, hi in tier:
+            pairs += [int(lo), int(hi)]
+    offs.append(off + len(pairs))
+    return np.asarray(head + offs + pairs, dtype=np.int32)
+
+
+def check_hypernode_table(tab, n_leaves: int) -> None:
+    """Shape rules of a mode-3 table (host numpy int32): the kernel trusts
+    the offsets, so they are checked before any launch."""
+    n = tab.shape[0]
+    if tab.ndim != 1 or n < 7:
+        raise ValueError("hypernode table: too short")
+    T, need = int(tab[0]), int(tab[1])
+    if T < 1 or need < 1:
+        raise ValueError("hypernode table: T and need must be >= 1")
+    if n < 6 + T:
+        raise ValueError("hypernode table: tier offsets cut short")
+    offs = tab[5:6 + T].astype("int64")
+    if offs[0] != 6 + T or (offs[1:] < offs[:-1]).any() or offs[-1] != n \
+            or ((offs[1:] - offs[:-1]) % 2).any():
+        raise ValueError("hypernode table: tier offsets must ascend from "
+                         "the end of the header to the end of the table in "
+                         "steps of whole pairs")
+    pairs = tab[6 + T:].reshape(-1, 2)
+    if ((pairs[:, 0] < 0) | (pairs[:, 1] < pairs[:, 0])
+            | (pairs[:, 1] > n_leaves)).any():
+        raise ValueError("hypernode table: a leaf range lies outside "
+                         "0 <= lo <= hi <= D")
+
+
+def hypernode_choice(cap, leaf_of, table, n_leaves: int):
+    """The winning ``(lo, hi)`` leaf range of ``hypernode_mask``, or None.
+    Plain Python integers throughout — no width to overflow."""
+    D = int(n_leaves)
+    tab = [int(x) for x in table.tolist()]
+    T, need, pin_lo, pin_hi = tab[0], tab[1], tab[2], tab[3]
+    if T < 1 or need < 1:
+        raise ValueError("hypernode table: T and need must be >= 1")
+    L = [0] * D
+    for c, leaf in zip(cap.tolist(), leaf_of.tolist()):
+        if 0 <= leaf < D:
+            L[leaf] += int(c)
+    P = [0] * (D + 1)
+    for d in range(D):
+        P[d + 1] = P[d] + L[d]
+    for t in range(T):
+        o0, o1 = tab[HN_TAB_HEAD + t], tab[HN_TAB_HEAD + t + 1]
+        best = None
+        for k in range((o1 - o0) // 2):
+            lo, hi = tab[o0 + 2 * k], tab[o0 + 2 * k + 1]
+            if lo < 0 or hi < lo or hi > D:
+                continue
+            if lo > pin_lo or pin_hi > hi:
+                continue
+            C = P[hi] - P[lo]
+            if C >= need and (best is None or C < best[0]):
+                best = (C, lo, hi)
+        if best is not None:
+            return best[1], best[2]
+    return None
+
+
+def hypernode_mask(
+    score: torch.Tensor,        # [N] f32 from score_cap, in place
+    cap: torch.Tensor,          # [N] i32, in place
+    leaf_of: torch.Tensor,      # [N] i32 leaf id in [0, D), -1 = no hypernode
+    table: torch.Tensor,        # the group's int32 table (hypernode_table)
+    n_leaves: int,              # D
+) -> None:
+    """Confine one class to ONE network domain (hypernode), chosen from the
+    live per-node ``cap`` — the source of truth for mode 3 of the HIP
+    ``domain_mask``.
+
+    Leaves are numbered depth-first, so a hypernode of any tier is a leaf
+    range ``[lo, hi)`` and its capacity the sum of ``cap`` over it.  Tiers
+    are tried lowest first; within a tier the eligible domain (containing
+    the pin) with the smallest capacity ``>= need`` wins, ties to the lower
+    table index.  Nodes outside the winner — unlabelled ones included — get
+    ``score = -inf``, ``cap = 0``; kept nodes are untouched.  Without a
+    winner hard mode masks every node, soft mode none.  The ordinary
+    ``select_commit`` follows.
+    """
+    win = hypernode_choice(cap, leaf_of, table, n_leaves)
+    if win is None:
+        if int(table[4]) != 0:
+            return
+        win = (0, 0)
+    leaf = leaf_of.to(torch.int64)
+    out = (leaf < win[0]) | (leaf >= win[1])
+    score[out] = NEG_INF
+    cap[out] = 0
 
 
 def drf_share(job_alloc: torch.Tensor, total: torch.Tensor) -> torch.Tensor:

@@ -29,6 +29,7 @@ from ...api.types import PodGroupPhase, TaskStatus
 PENDING_S = TaskStatus.PENDING
 BOUND_S = TaskStatus.BOUND
 from ...ops import host
+from ...ops import reference as ref_ops
 from ...utils.metrics import METRICS
 from ..plan import (BundleEntry, ClassPlan, CyclePlan, JobPlan, run_plan_hip,
                     run_plan_torch)
@@ -283,6 +284,35 @@ class AllocateAction:
                     cp.forbid[bit // 64] &= \
                         ~(np.int64(1) << np.int64(bit % 64))
 
+        # exact network topology (network-topology-aware plugin, ``exact:
+        # true``): a job that plans as ONE single-class gang, and every
+        # SubGroupPolicy subgroup with a topology override, has its
+        # hypernode chosen on the device from the live per-node capacity.
+        # Not under the soft-shard coordinator, as for spread.
+        hypernode_exact = getattr(ssn, "hypernode_exact", None) \
+            if self.coordinator is None else None
+        hypernode_row: List[int] = []            # the plan's one leaf row
+
+        def hypernode_attach(cp: ClassPlan, job, hn, need: int) -> None:
+            """Route cp through the hypernode mask.  The caller built its
+            constraint words with ``skip_topology``: the host scan over the
+            domains never ran and no ``hn:`` (or nowhere) bit is set."""
+            tiers, pin, soft = hn
+            if not hypernode_row:
+                hypernode_row.append(plan.add_hypernode_row(
+                    hypernode_exact.leaf_of, hypernode_exact.n_leaves))
+            cp.hypernode = plan.add_hypernode_group(
+                hypernode_row[0], ref_ops.hypernode_table(
+                    tiers, max(1, int(need)), hypernode_exact.n_leaves,
+                    pin, soft))
+
+        if hypernode_exact is not None and elig_l is not None:
+            # each such job needs its own domain: none joins a fused run
+            for ix, jb in enumerate(jobs_l):
+                if elig_l[ix] and \
+                        hypernode_exact.resolve_job(jb) is not None:
+                    elig_l[ix] = False
+
         # such jobs never join a fused signature run
         if (spread_exact is not None or affinity_exact is not None) \
                 and elig_l is not None:
@@ -393,7 +423,8 @@ class AllocateAction:
                     job.podgroup.spec.sub_group_policy:
                 close_bundle()
                 self._plan_subgroups(ssn, plan, job, qi, predicates,
-                                     w_least, w_most, w_bal)
+                                     w_least, w_most, w_bal,
+                                     hypernode_exact, hypernode_attach)
                 continue
 
             # -- nomination fast path (reference allocate.go:797
@@ -422,7 +453,11 @@ class AllocateAction:
                     if spread_exact is not None else None
                 af = affinity_exact.resolve_task(first) \
                     if affinity_exact is not None and sp is None else None
-                if sp is None and af is None and not bias_fns \
+                hn = hypernode_exact.resolve_job(job) \
+                    if hypernode_exact is not None and sp is None \
+                    and af is None else None
+                if sp is None and af is None and hn is None \
+                        and not bias_fns \
                         and open_bundle is not None \
                         and open_key == (qi, sig):
                     tasks = list(pend.values())
@@ -439,8 +474,11 @@ class AllocateAction:
                     if gang_min < b.min_needed:
                         b.min_needed = gang_min
                     continue
+                # a hypernode job's words are built without the topology
+                # hook (no host scan over the domains), so they are not
+                # the memoized ones
                 ckey = (sig, qi)
-                got = cons_memo.get(ckey, _MISS)
+                got = cons_memo.get(ckey, _MISS) if hn is None else _MISS
                 if got is _MISS:
                     req = nt.req_vector(first)
                     if req is None:
@@ -451,14 +489,16 @@ class AllocateAction:
                                         priority=priority)
                         if predicates is not None:
                             tol, require, forbid = \
-                                predicates.class_constraints(tc0, job)
+                                predicates.class_constraints(
+                                    tc0, job, skip_topology=hn is not None)
                         else:
                             tol = -1
                             W = max(nt.labels.words, 1)
                             require = np.zeros(W, dtype=np.int64)
                             forbid = np.zeros(W, dtype=np.int64)
                         got = (req, tol, require, forbid)
-                    cons_memo[ckey] = got
+                    if hn is None:
+                        cons_memo[ckey] = got
                 if got is None:
                     continue      # asks for a resource no node offers
                 req, tol, require, forbid = got
@@ -479,9 +519,12 @@ class AllocateAction:
                     spread_attach(cp, sp)
                 elif af is not None:
                     affinity_attach(cp, af)
+                elif hn is not None:
+                    hypernode_attach(cp, job, hn, gang_min)
                 # biased and domain-rule classes never fuse
                 if cp.bias is not None or cp.spread is not None \
-                        or cp.affinity is not None:
+                        or cp.affinity is not None \
+                        or cp.hypernode is not None:
                     close_bundle()
                     plan.add_job(job, [cp])
                 else:
@@ -490,15 +533,28 @@ class AllocateAction:
 
             classes: List[ClassPlan] = []
             skipped = False
-            for tc in job.pending_classes():
-                if tc.tasks[0].best_effort:
-                    continue    # BestEffort is backfill's (allocate.go:265)
+            pending = [tc for tc in job.pending_classes()
+                       if not tc.tasks[0].best_effort]
+            # BestEffort is backfill's (allocate.go:265).  A job whose
+            # pending tasks form ONE class may have its hypernode chosen on
+            # the device: resolved before the constraints are built, so
+            # that the topology hook's host scan never runs for it
+            hn = None
+            if hypernode_exact is not None and len(pending) == 1 and not (
+                    (spread_exact is not None and spread_exact.resolve_task(
+                        pending[0].tasks[0]) is not None) or
+                    (affinity_exact is not None and
+                     affinity_exact.resolve_task(
+                         pending[0].tasks[0]) is not None)):
+                hn = hypernode_exact.resolve_job(job)
+            for tc in pending:
                 req = nt.req_vector(tc.tasks[0])
                 if req is None:
                     skipped = True    # asks for a resource no node offers
                     continue
                 if predicates is not None:
-                    tol, require, forbid = predicates.class_constraints(tc, job)
+                    tol, require, forbid = predicates.class_constraints(
+                        tc, job, skip_topology=hn is not None)
                 else:
                     tol = -1          # tolerate everything
                     W = max(nt.labels.words, 1)
@@ -528,12 +584,18 @@ class AllocateAction:
                 continue
             if not classes:
                 continue
+            if hn is not None:
+                hypernode_attach(
+                    classes[0], job, hn,
+                    max(job.min_available - job.occupied_count,
+                        classes[0].min_needed))
 
             bundleable = (len(classes) == 1 and job.occupied_count == 0
                           and classes[0].tclass.count == len(job.tasks)
                           and classes[0].bias is None
                           and classes[0].spread is None
-                          and classes[0].affinity is None)
+                          and classes[0].affinity is None
+                          and classes[0].hypernode is None)
             if bundleable:
                 cp = classes[0]
                 gang_min = max(job.min_available, cp.min_needed)
@@ -568,7 +630,8 @@ class AllocateAction:
         METRICS.observe("allocate:apply", t3 - t2)
 
     def _plan_subgroups(self, ssn, plan, job, qi: int, predicates,
-                        w_least, w_most, w_bal) -> None:
+                        w_least, w_most, w_bal, hypernode_exact=None,
+                        hypernode_attach=None) -> None:
         """Partition the job's pending pods per SubGroupPolicy entry and
         emit one single-class gang JobPlan per complete subgroup.  Pods
         left unmatched (or in an incomplete tail chunk) stay pending
@@ -621,9 +684,15 @@ class AllocateAction:
                                    role=first.role, request=first.request,
                                    tasks=chunk, priority=first.priority,
                                    topology=topo)
+                    # exact network topology: the subgroup's domain is
+                    # chosen on the device — the host hook (and its
+                    # reservation ledger) is not consulted
+                    hn = hypernode_exact.resolve_spec(topo) \
+                        if hypernode_exact is not None and topo else None
                     if predicates is not None:
                         tol, require, forbid = \
-                            predicates.class_constraints(tc, job)
+                            predicates.class_constraints(
+                                tc, job, skip_topology=hn is not None)
                     else:
                         W = max(ssn.node_tensors.labels.words, 1)
                         tol = -1
@@ -636,6 +705,8 @@ class AllocateAction:
                                    forbid=forbid, min_needed=size,
                                    w_least=w_least, w_most=w_most,
                                    w_bal=w_bal)
+                    if hn is not None:
+                        hypernode_attach(cp, job, hn, size)
                     plan.jobs.append(JobPlan(
                         job_key=skey, class_begin=len(plan.classes),
                         class_end=len(plan.classes) + 1, occupied=0,

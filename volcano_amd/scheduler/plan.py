@@ -63,6 +63,11 @@ class SpreadGroup:
     nothing is read back — the next session recounts from task statuses."""
     dom_of: np.ndarray         # [N] i32, -1 = node lacks the topology label
     count: np.ndarray          # [D] i32, 1 <= D <= N
+    # network-topology group (ClassPlan.hypernode): ``dom_of`` is the
+    # shared leaf row ``row`` of CyclePlan.hypernode_rows, ``count`` the
+    # read-only table of the rule, ``leaves`` the row's leaf count
+    row: int = -1
+    leaves: int = 0
 
 
 @dataclass(slots=True)
@@ -104,6 +109,11 @@ class ClassPlan:
     # the group's domains — domain mask + select_commit + count update.
     # Never combined with ``bundle`` or ``spread``.
     affinity: Optional[Tuple[int, int]] = None
+    # index into CyclePlan.spread_groups of a network-topology group
+    # (add_hypernode_group): domain mask mode 3 + select_commit, the domain
+    # chosen on the device from the live cap.  Never combined with
+    # ``bundle``, ``spread`` or ``affinity``.
+    hypernode: Optional[int] = None
 
     @property
     def ntasks(self) -> int:
@@ -193,6 +203,42 @@ class CyclePlan:
         # live per-domain counts of the last run (device tensors, one per
         # group) — left for inspection, never copied to the host here
         self.spread_counts = None
+        # leaf_of rows ([N] i32, leaf count) shared by network-topology
+        # groups, and the groups already made per (row, table)
+        self.hypernode_rows: List[Tuple[np.ndarray, int]] = []
+        self._hypernode_groups: Dict[Tuple[int, bytes], int] = {}
+
+    def add_hypernode_row(self, leaf_of, n_leaves: int) -> int:
+        """Register a node → leaf map (leaves numbered depth-first over
+        the HyperNode tree); every group built on it shares the upload."""
+        leaf_of = np.ascontiguousarray(leaf_of, dtype=np.int32)
+        if leaf_of.shape != (self.nt.n,):
+            raise ValueError("hypernode row: leaf_of needs one entry per "
+                             "node")
+        if not 1 <= int(n_leaves) <= max(self.nt.n, 1):
+            raise ValueError("hypernode row: leaf count outside [1, N]")
+        if leaf_of.max(initial=-1) >= n_leaves or \
+                leaf_of.min(initial=0) < -1:
+            raise ValueError("hypernode row: leaf id out of range")
+        self.hypernode_rows.append((leaf_of, int(n_leaves)))
+        return len(self.hypernode_rows) - 1
+
+    def add_hypernode_group(self, row_id: int, table) -> int:
+        """One network-topology rule (``ref.hypernode_table``) over leaf
+        row ``row_id``.  Identical (T, need, pin, soft, ranges) share one
+        group, hence one table slice."""
+        if not 0 <= row_id < len(self.hypernode_rows):
+            raise ValueError(f"hypernode group: unknown row {row_id}")
+        table = np.ascontiguousarray(table, dtype=np.int32)
+        leaf_of, leaves = self.hypernode_rows[row_id]
+        key = (row_id, table.tobytes())
+        g = self._hypernode_groups.get(key)
+        if g is None:
+            ref.check_hypernode_table(table, leaves)
+            self.spread_groups.append(
+                SpreadGroup(leaf_of, table, row=row_id, leaves=leaves))
+            g = self._hypernode_groups[key] = len(self.spread_groups) - 1
+        return g
 
     def add_spread_group(self, dom_of, count) -> int:
         dom_of = np.ascontiguousarray(dom_of, dtype=np.int32)
@@ -275,6 +321,21 @@ class CyclePlan:
                 if cp.spread is not None:
                     raise ValueError(f"class {c}: one domain rule per class "
                                      "(spread and affinity both set)")
+            if cp.hypernode is not None:
+                g = cp.hypernode
+                if not 0 <= g < len(self.spread_groups) or \
+                        self.spread_groups[g].row < 0:
+                    raise ValueError(f"class {c}: unknown hypernode group "
+                                     f"{g}")
+                if cp.bundle is not None:
+                    raise ValueError(f"class {c}: hypernode classes never "
+                                     "bundle")
+                if cp.spread is not None or cp.affinity is not None:
+                    raise ValueError(f"class {c}: one domain rule per class")
+            for rule in (cp.spread, cp.affinity):
+                if rule is not None and self.spread_groups[rule[0]].row >= 0:
+                    raise ValueError(f"class {c}: group {rule[0]} is a "
+                                     "hypernode group")
         self.log_total = off
         lens = np.fromiter((jp.class_end - jp.class_begin
                             for jp in self.jobs), dtype=np.int64,
@@ -364,6 +425,15 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
                     log_nodes[sl], log_counts[sl], log_len[c],
                     class_placed[c], job_placed[j],
                     sp_dom[g], sp_cnt[g], skew)
+            elif cp.hypernode is not None:
+                g = cp.hypernode
+                ref.hypernode_mask(score, cap, sp_dom[g], sp_cnt[g],
+                                   plan.spread_groups[g].leaves)
+                ref.select_commit(score, cap, req, cp.ntasks, used,
+                                  plan.queue_alloc[cp.queue_idx],
+                                  plan.queue_limit[cp.queue_idx],
+                                  log_nodes[sl], log_counts[sl], log_len[c],
+                                  class_placed[c], job_placed[j])
             elif cp.affinity is not None:
                 g, mode = cp.affinity
                 ref.affinity_select_commit(
@@ -495,8 +565,10 @@ def run_plan_hip(plan: CyclePlan) -> CycleResult:
     # when the plan has affinity classes — otherwise the call is the one a
     # spread-only plan always made.
     spread = None
+    any_hn = any(cp.hypernode is not None for cp in plan.classes)
     any_aff = any(cp.affinity is not None for cp in plan.classes)
-    if any_aff or any(cp.spread is not None for cp in plan.classes):
+    if any_hn or any_aff or \
+            any(cp.spread is not None for cp in plan.classes):
         groups = plan.spread_groups
         cg = np.full(C, -1, dtype=np.int32)
         cs = np.ones(C, dtype=np.int32)
@@ -506,22 +578,45 @@ def run_plan_hip(plan: CyclePlan) -> CycleResult:
                 cg[c], cs[c] = cp.spread
             elif cp.affinity is not None:
                 cg[c], cm[c] = cp.affinity
-        doms = np.array([g.count.shape[0] for g in groups], dtype=np.int32)
-        offs = (np.cumsum(doms) - doms).astype(np.int32)
+            elif cp.hypernode is not None:
+                cg[c], cm[c] = cp.hypernode, ref.HYPERNODE
+        # a hypernode group's slice of `count` is its table and its D the
+        # leaf count of its row
+        lens = np.array([g.count.shape[0] for g in groups], dtype=np.int32)
+        doms = np.array([g.leaves if g.row >= 0 else g.count.shape[0]
+                         for g in groups], dtype=np.int32)
+        offs = (np.cumsum(lens) - lens).astype(np.int32)
         count = torch.from_numpy(
             np.concatenate([g.count for g in groups]).astype(np.int32)
         ).to(dev)
+        # dom_of rows: one per ordinary group, ONE per leaf map however
+        # many hypernode groups read it (group_row names the row)
+        rows: List[np.ndarray] = []
+        row_of_leafmap: Dict[int, int] = {}
+        grow = np.empty(len(groups), dtype=np.int32)
+        for gi, g in enumerate(groups):
+            if g.row >= 0:
+                r = row_of_leafmap.get(g.row)
+                if r is None:
+                    r = row_of_leafmap[g.row] = len(rows)
+                    rows.append(g.dom_of)
+                grow[gi] = r
+            else:
+                grow[gi] = len(rows)
+                rows.append(g.dom_of)
         spread = dict(
             class_group=cg, class_skew=cs,
             dom_of=torch.from_numpy(
-                np.stack([g.dom_of for g in groups]).astype(np.int32)
+                np.stack(rows).astype(np.int32)
             ).to(dev).contiguous(),
             count=count, count_off=offs, domains=doms,
             scratch=hip.spread_scratch(N, dev))
-        if any_aff:
+        if any_aff or any_hn:
             spread["class_mode"] = cm
+        if row_of_leafmap:
+            spread["group_row"] = grow
         plan.spread_counts = [count[int(o):int(o) + int(d)]
-                              for o, d in zip(offs, doms)]
+                              for o, d in zip(offs, lens)]
 
     hip.run_cycle(
         ctypes.c_void_p(cds.ctypes.data), C,

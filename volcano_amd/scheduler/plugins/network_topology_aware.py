@@ -14,17 +14,143 @@ and the chosen domain rides the predicate kernel as one require bit.
 Hard mode: no feasible domain ⇒ the job's classes get an impossible
 require bit (never placed this cycle).  Soft mode: feasible domain
 preferred, otherwise unconstrained.
+
+Plugin argument ``exact`` (default ``false``): with ``exact: true`` the
+domain is chosen ON THE DEVICE, per class, from the live per-node
+capacity the score kernel just computed (``ops/reference.py
+hypernode_mask`` / mode 3 of ``vamd_domain_mask``).  The choice then sees
+everything placed earlier in the same cycle, fragmentation (a rack whose
+free memory no single pod fits has capacity 0) and every predicate, and
+within the lowest feasible tier it takes the tightest fit.  The plugin
+publishes ``ssn.hypernode_exact``: the depth-first leaf numbering that
+makes every hypernode one contiguous leaf range, ``leaf_of[N]``, the
+``(lo, hi)`` lists per tier and ``resolve_job``.  A direct ``Node`` member
+of a non-leaf hypernode gets a pseudo-leaf inside its parent's range.
+
+The allocate action routes this way the jobs that plan as ONE single-class
+gang and every SubGroupPolicy subgroup with a ``networkTopology`` override
+(each subgroup its own rule, no pin, no reservation ledger).  The host
+choice above stays in force for multi-class jobs (the first class's choice
+would have to reach the later classes on the device), for jobs with a
+placed task on a node outside every hypernode, for HyperNode sets that are
+not laminar (a node in two hypernodes neither of which contains the other;
+logged once), under the soft-shard coordinator, and for backfill, preempt
+and the nominated fast path.
 """
 
 from __future__ import annotations
 
-from typing import Dict, Optional
+import logging
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
 from ...api.hypernode import HyperNodeTree
 from ..tensors import set_plane_bit
 from .base import Plugin, register
+
+
+log = logging.getLogger(__name__)
+
+
+def _truthy(v) -> bool:
+    if isinstance(v, str):
+        return v.strip().lower() in ("1", "true", "yes", "on")
+    return bool(v)
+
+
+class HypernodeExact:
+    """What ``exact: true`` publishes on the session
+    (``ssn.hypernode_exact``)."""
+
+    def __init__(self, leaf_of: np.ndarray, n_leaves: int,
+                 tiers: List[int], ranges: List[List[Tuple[int, int]]],
+                 leaf_by_node: Dict[str, int]):
+        self.leaf_of = leaf_of          # [N] i32, -1 = in no hypernode
+        self.n_leaves = n_leaves        # D
+        self.tiers = tiers              # distinct tier values, ascending
+        self.ranges = ranges            # per tier: (lo, hi), ascending lo
+        self.leaf_by_node = leaf_by_node
+
+    def tiers_upto(self, max_tier) -> List[List[Tuple[int, int]]]:
+        return [r for t, r in zip(self.tiers, self.ranges)
+                if max_tier is None or t <= max_tier]
+
+    def resolve_spec(self, spec, placed_nodes=()):
+        """(tier lists, pin or None, soft) of a networkTopology spec, or
+        None when the host path must decide (no tier allowed, or a placed
+        task outside every hypernode)."""
+        if not spec:
+            return None
+        tiers = self.tiers_upto(spec.get("highestTierAllowed"))
+        if not tiers:
+            return None
+        pin = None
+        if placed_nodes:
+            leaves = [self.leaf_by_node.get(n) for n in placed_nodes]
+            if any(l is None for l in leaves):
+                return None
+            pin = (min(leaves), max(leaves) + 1)
+        return tiers, pin, spec.get("mode", "hard") != "hard"
+
+    def resolve_job(self, job):
+        """``resolve_spec`` of the job's PodGroup, pinned to the leaf range
+        its already-placed tasks span."""
+        spec = job.podgroup.spec.network_topology \
+            if job is not None and job.podgroup is not None else None
+        if not spec:
+            return None
+        return self.resolve_spec(
+            spec, {t.node_name for t in job.tasks.values() if t.node_name})
+
+
+def number_leaves(tree: HyperNodeTree, node_ids: Dict[str, int],
+                  n: int) -> Optional[HypernodeExact]:
+    """Depth-first leaf numbering of the HyperNode tree: afterwards every
+    hypernode of every tier is one contiguous leaf range.  None when the
+    set is not laminar or holds no node."""
+    children: Dict[str, List[str]] = {}
+    for child, parent in tree.parent.items():
+        children.setdefault(parent, []).append(child)
+    leaf_by_node: Dict[str, int] = {}
+    span: Dict[str, Tuple[int, int]] = {}
+    nxt = 0
+
+    def walk(h: str) -> bool:
+        nonlocal nxt
+        lo = nxt
+        below = set()
+        for c in sorted(children.get(h, ())):
+            if c in span or not walk(c):
+                return False
+            below |= tree.members[c]
+        direct = sorted(m for m in tree.members[h] - below if m in node_ids)
+        if direct:                      # (pseudo-)leaf of the direct nodes
+            for m in direct:
+                if m in leaf_by_node:
+                    return False
+                leaf_by_node[m] = nxt
+            nxt += 1
+        span[h] = (lo, nxt)
+        return True
+
+    roots = sorted(h for h in tree.members if h not in tree.parent)
+    if not all(walk(r) for r in roots) or nxt == 0:
+        return None
+    # every hypernode must own exactly the nodes of its leaf range
+    for h, (lo, hi) in span.items():
+        mine = {m for m in tree.members[h] if m in node_ids}
+        if mine != {m for m, l in leaf_by_node.items() if lo <= l < hi}:
+            return None
+    if len(span) != len(tree.members):
+        return None
+    leaf_of = np.full(n, -1, dtype=np.int32)
+    for m, l in leaf_by_node.items():
+        leaf_of[node_ids[m]] = l
+    tiers = sorted(set(tree.tier[h] for h in span))
+    ranges = [sorted((span[h] for h in span if tree.tier[h] == t))
+              for t in tiers]
+    return HypernodeExact(leaf_of, nxt, tiers, ranges, leaf_by_node)
 
 
 @register("network-topology-aware")
@@ -39,6 +165,15 @@ class NetworkTopologyAwarePlugin(Plugin):
             hypernodes, list(ssn.nodes),
             {n: ni.node.meta.labels for n, ni in ssn.nodes.items()})
         ssn.hypernode_tree = tree
+        if _truthy(self.args.get("exact", False)):
+            published = number_leaves(
+                tree, {n: ni.node_id for n, ni in ssn.nodes.items()}, nt.n)
+            if published is None:
+                log.warning("network-topology-aware: the HyperNode set is "
+                            "not laminar; exact domain choice is off for "
+                            "this session")
+            else:
+                ssn.hypernode_exact = published
 
         # per-domain: node ids, free capacity vector, membership bit
         self.domain_ids: Dict[str, list] = {}
