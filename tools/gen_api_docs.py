@@ -29,6 +29,25 @@ GROUPS = {
 }
 
 
+# hand-written tail: scheduler plugin arguments that change what a Pod's
+# annotations mean to the allocate cycle
+PLUGIN_ARGS = """\
+## Scheduler plugin arguments
+
+- `deviceshare` — `exact` (default `false`): pack the slices that the Pod
+  annotations `volcano.sh/gpu-number` / `volcano.sh/gpu-memory` and
+  `volcano.sh/vgpu-number` / `volcano.sh/vgpu-memory` / `volcano.sh/vgpu-cores`
+  ask for per card inside the allocate cycle, per placement, on the device.
+  Every bound Pod with a device request then carries `volcano.sh/gpu-index`;
+  a Pod the cards cannot pack stays pending.  Needs at most 16 cards per
+  Node, cards of one size on each Node and `volcano.sh/gpu-memory-per-card`
+  below 2^28 MiB; otherwise, and under the soft-shard coordinator, the
+  session-open check is used.
+  Also: `deviceshare.schedule-policy` (`binpack` | `spread`),
+  `deviceshare.gpu-score-weight`.
+"""
+
+
 def type_name(t) -> str:
     s = str(t).replace("typing.", "")
     for tok in ("volcano_amd.api.objects.", "volcano_amd.api.resource.",
@@ -58,6 +77,7 @@ def main() -> None:
                     continue
                 out.append(f"- `{f.name}`: {type_name(f.type)}")
         out.append("")
+    out.append(PLUGIN_ARGS)
     path = os.path.join(os.path.dirname(os.path.dirname(
         os.path.abspath(__file__))), "docs", "api.md")
     with open(path, "w") as fh:

@@ -103,19 +103,35 @@ struct ClassView {
     int group, mode, skew, D;
     const int32_t* dom_of;       // [N]
     int32_t* dom_count;          // [D]
+    // device request (count, memory, cores); null = none
+    const int32_t* dev;
 };
 
 struct Runner {
     const VamdCycle& cy;
     hipStream_t stream;
     const bool domains_live;
+    const bool devices_live;
 
     Runner(const VamdCycle& c, hipStream_t s)
         : cy(c), stream(s),
           domains_live(c.class_group != nullptr && c.dom_of != nullptr &&
-                       c.count != nullptr && c.domain_scratch != nullptr) {}
+                       c.count != nullptr && c.domain_scratch != nullptr),
+          devices_live(c.card_mem_used != nullptr &&
+                       c.card_cores_used != nullptr &&
+                       c.card_state != nullptr &&
+                       c.card_mem_total != nullptr &&
+                       c.class_dev_req != nullptr &&
+                       c.dev_assign != nullptr && c.card_K >= 1) {}
 
     int group_of(int c) const { return domains_live ? cy.class_group[c] : -1; }
+
+    // the class's device request row, or null
+    const int32_t* dev_of(int c) const {
+        if (!devices_live) return nullptr;
+        const int32_t* rq = cy.class_dev_req + (size_t)c * 4;
+        return rq[0] > 0 ? rq : nullptr;
+    }
 
     ClassView view(int j, int c) const {
         const VamdClassDesc& cd = cy.classes[c];
@@ -132,7 +148,7 @@ struct Runner {
             cy.log_nodes + cd.log_off, cy.log_counts + cd.log_off,
             cy.log_len + c, cy.class_placed + c, cy.job_placed + j,
             cy.job_flag + j, single ? gang_fuse_min(job, cd) : -1,
-            g, 0, 0, 0, nullptr, nullptr};
+            g, 0, 0, 0, nullptr, nullptr, dev_of(c)};
         if (g >= 0) {
             v.mode = cy.class_mode != nullptr ? cy.class_mode[c] : 0;
             if (v.mode == 0) v.skew = cy.class_skew[c];
@@ -190,7 +206,30 @@ struct Runner {
                               v.dom_count, v.D, cy.N, v.cd.log_cap, stream);
     }
 
+    void device_cap(const ClassView& v) const {
+        vamd_device_cap(cy.score_scratch, cy.cap_scratch, cy.card_mem_used,
+                        cy.card_cores_used, cy.card_state, cy.card_mem_total,
+                        v.dev[0], v.dev[1], v.dev[2], cy.card_K, cy.N,
+                        stream);
+    }
+
+    void device_commit(const ClassView& v) const {
+        vamd_device_commit(v.log_nodes, v.log_counts, v.log_len,
+                           cy.card_mem_used, cy.card_cores_used,
+                           cy.card_state, cy.card_mem_total,
+                           cy.dev_assign + (size_t)v.cd.log_off * cy.card_K,
+                           v.dev[0], v.dev[1], v.dev[2], cy.card_K, cy.N,
+                           v.cd.log_cap, stream);
+    }
+
     void revert(const ClassView& v) const {
+        // the card planes give back what the assignment rows recorded
+        if (v.dev != nullptr)
+            vamd_device_revert(
+                v.job_flag, v.log_nodes, v.log_len, cy.card_mem_used,
+                cy.card_cores_used, cy.card_state,
+                cy.dev_assign + (size_t)v.cd.log_off * cy.card_K, v.dev[1],
+                v.dev[2], cy.card_K, cy.N, v.cd.log_cap, stream);
         // a network-topology class holds a table, not counts: plain revert
         if (v.group >= 0 && v.mode != MODE_HYPERNODE) {
             vamd_spread_revert(v.job_flag, v.log_nodes, v.log_counts,
@@ -204,8 +243,27 @@ struct Runner {
                          v.job_placed, cy.N, cy.R, stream);
     }
 
+    // A class with a device request: always the split path, the per-card
+    // clamp right after the score so that every domain rule reads the
+    // clamped cap, the slices taken after the select (and count update).
+    void run_device_class(const ClassView& v) const {
+        score(v);
+        device_cap(v);
+        if (v.group >= 0 && v.mode == 0) {
+            spread_select(v);
+        } else {
+            if (v.group >= 0) domain_mask(v);
+            select(v);
+            if (v.group >= 0 && v.mode != MODE_HYPERNODE)
+                domain_count_add(v);
+        }
+        device_commit(v);
+    }
+
     void run_class(const ClassView& v) const {
-        if (v.group >= 0 && v.mode == MODE_HYPERNODE) {
+        if (v.dev != nullptr) {
+            run_device_class(v);
+        } else if (v.group >= 0 && v.mode == MODE_HYPERNODE) {
             // network topology: the mask confines the class to the one
             // hypernode chosen from the live cap; the group's slice is a
             // read-only table, so no count update follows
@@ -254,12 +312,13 @@ struct Runner {
             revert(view(j, c));
     }
 
-    // a single-class small job without a domain rule; anything else
-    // breaks a chain run
+    // a single-class small job without a domain rule or device request;
+    // anything else breaks a chain run
     bool chainable(int j) const {
         const VamdJobDesc& jb = cy.jobs[j];
         return jb.class_end - jb.class_begin == 1 &&
             group_of(jb.class_begin) < 0 &&
+            dev_of(jb.class_begin) == nullptr &&
             cy.classes[jb.class_begin].ntasks < BULK_TASKS;
     }
 
@@ -274,13 +333,14 @@ struct Runner {
         return e;
     }
 
-    // The megacycle kernel has no bulk and no domain-rule select: such a
-    // plan runs per class.  False as well when the staging allocation
+    // The megacycle kernel has no bulk, no domain-rule select and no card
+    // planes: such a plan runs per class.  False as well when the staging allocation
     // fails: fall through to per-class launches.
     bool try_megacycle() const {
         if (cy.n_classes < 32) return false;
         for (int c = 0; c < cy.n_classes; ++c)
-            if (cy.classes[c].ntasks >= BULK_TASKS || group_of(c) >= 0)
+            if (cy.classes[c].ntasks >= BULK_TASKS || group_of(c) >= 0 ||
+                    dev_of(c) != nullptr)
                 return false;
         void* blob;
         VamdDevDescs dd;

@@ -1349,6 +1349,205 @@ __global__ void domain_count_add_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Device share: per-card packing of GPU slices, per placement.
+//
+// Oracle: GPUDevicePool.allocate called once per pod (api/devices.py) —
+// each pod picks `count` slices best-fit: the fullest feasible card first
+// (mem_used larger wins, strictly), ties to the lower card index.  Two facts
+// make that closed-form, so nothing is simulated here:
+//   * capacity: a slice takes (memory, cores) from ONE card and cards are
+//     independent, so card k has a fixed number of slots for a request
+//     shape (card_slots); with S = sum of slots a node packs exactly
+//     floor(S / count) pods, whatever the order;
+//   * fill order: the chosen card only gets fuller, so it stays the strict
+//     maximum until it has no slot left; m pods in a row fill the cards in
+//     the order (mem_used desc, index asc) among cards with slots, each to
+//     its slot count, and pod i owns positions [i*count, (i+1)*count) of
+//     that sequence.
+// Card planes are int32 [K, N] (K <= 16 cards, card-major like the resource
+// planes: a wave reads 64 consecutive nodes of one card index); card_state
+// is the slice count with DS_GONE set for an exclusive or absent card.
+// mem_total < 2^28 (host-checked), so every product below fits int32 and
+// S <= 16 * 2^28 is summed in int64.
+// ---------------------------------------------------------------------------
+#define DS_MAX_CARDS 16
+#define DS_GONE (1 << 30)
+#define DS_TAKE_BITS 28
+#define DS_TAKE_MASK ((1u << DS_TAKE_BITS) - 1u)
+#define DS_THREADS 256
+#define DS_ENTRIES_PER_WAVE (WAVE / DS_MAX_CARDS)
+
+// slots of one card for one slice shape (Card.fits, counted); the caller
+// has ruled out DS_GONE, and an exclusive request reads `state` alone
+DEVINL int card_slots(int mem_used, int cores_used, int state, int mem_total,
+                      int memory, int cores)
+{
+    if (memory == 0 && cores == 0) return state == 0 ? 1 : 0;
+    if (mem_used > mem_total) return 0;
+    int s = 0x7fffffff;
+    if (memory > 0) s = (mem_total - mem_used) / memory;
+    if (cores > 0) s = min(s, (100 - cores_used) / cores);
+    return max(s, 0);
+}
+
+// `take` slices of the shape join (dir = 1) or leave (dir = -1) one card
+DEVINL void card_apply(int* __restrict__ mem_used, int* __restrict__ cores_used,
+                       int* __restrict__ state, size_t o, int take,
+                       int memory, int cores, int dir)
+{
+    int st = state[o];
+    if (memory == 0 && cores == 0) {
+        st = dir > 0 ? ((st + take) | DS_GONE) : ((st & ~DS_GONE) - take);
+    } else {
+        st += dir * take;
+        if (memory > 0) mem_used[o] += dir * take * memory;
+        if (cores > 0) cores_used[o] += dir * take * cores;
+    }
+    state[o] = st;
+}
+
+// After score_cap, before any domain rule: cap = min(cap, S / count), and
+// score = -inf where that leaves nothing (score > -inf <=> cap > 0 holds).
+// Grid-stride, one thread per node; a node with cap == 0 loads nothing.
+// The card loop is unrolled over the compile-time bound KB, so no card is
+// ever indexed dynamically in registers.
+template <int KB>
+__global__ void device_cap_kernel(
+    float* __restrict__ score, int* __restrict__ cap,
+    const int* __restrict__ card_mem_used,
+    const int* __restrict__ card_cores_used,
+    const int* __restrict__ card_state,
+    const int* __restrict__ card_mem_total,
+    int count, int memory, int cores, int K, int N)
+{
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N;
+         i += gridDim.x * blockDim.x) {
+        const int c = cap[i];
+        if (c <= 0) continue;
+        const bool whole = memory == 0 && cores == 0;
+        const int total = whole ? 0 : card_mem_total[i];
+        long long S = 0;
+#pragma unroll
+        for (int k = 0; k < KB; ++k) {
+            if (k < K) {
+                const size_t o = (size_t)k * N + i;
+                const int st = card_state[o];
+                if (st & DS_GONE) continue;
+                // only the planes the shape is bound by are loaded
+                const int mu = whole ? 0 : card_mem_used[o];
+                const int cu = cores > 0 ? card_cores_used[o] : 0;
+                S += card_slots(mu, cu, st, total, memory, cores);
+            }
+        }
+        const long long fit = S / count;
+        if (fit < (long long)c) {
+            cap[i] = (int)fit;
+            if (fit == 0) score[i] = NEG_INF;
+        }
+    }
+}
+
+// After the select (and the domain count update): the logged placements
+// take their slices.  One 16-lane group per log entry (node, cnt), four
+// entries per wave, grid-stride over *log_len; lane k holds card k of the
+// entry's node.  rank = cards earlier in (mem_used desc, index asc) among
+// cards with slots, prefix = their slots, both by width-16 shuffles over
+// the 16 cards; take = clamp(cnt*count - prefix, 0, slots).  Each lane
+// updates its own card with plain stores and writes ONE word of the
+// entry's assignment row at position `rank`: card << 28 | take (cards
+// without a take fill the tail with 0).  A class logs a node at most once:
+// entries never share a card, so there are no atomics.  The loop bound is
+// the same for every lane of a wave — all 64 lanes stay active through the
+// shuffles.
+__global__ void __launch_bounds__(DS_THREADS) device_commit_kernel(
+    const int* __restrict__ log_nodes, const int* __restrict__ log_counts,
+    const int* __restrict__ log_len,
+    int* __restrict__ card_mem_used, int* __restrict__ card_cores_used,
+    int* __restrict__ card_state, const int* __restrict__ card_mem_total,
+    int* __restrict__ assign,             // [L, K]
+    int count, int memory, int cores, int K, int N, int L)
+{
+    int len = *log_len;
+    if (len > L) len = L;
+    const int k = threadIdx.x & (DS_MAX_CARDS - 1);
+    const int group = (blockIdx.x * blockDim.x + threadIdx.x) / DS_MAX_CARDS;
+    const int sub = group & (DS_ENTRIES_PER_WAVE - 1);
+    const int groups = gridDim.x * blockDim.x / DS_MAX_CARDS;
+    for (int base = group - sub; base < len; base += groups) {
+        const int e = base + sub;
+        const bool row = e < len && k < K;
+        int node = -1, cnt = 0;
+        if (row) { node = log_nodes[e]; cnt = log_counts[e]; }
+        const bool live = row && cnt > 0 && node >= 0 && node < N;
+        const size_t o = live ? (size_t)k * N + node : 0;
+        int mu = 0, slots = 0;
+        if (live) {
+            const int st = card_state[o];
+            if (!(st & DS_GONE)) {
+                mu = card_mem_used[o];
+                slots = card_slots(mu, cores > 0 ? card_cores_used[o] : 0, st,
+                                   card_mem_total[node], memory, cores);
+            }
+        }
+        // lanes with slots rank among themselves; the rest follow by index
+        int earlier = 0, with_slots = 0, empty_below = 0;
+        long long prefix = 0;
+#pragma unroll
+        for (int j = 0; j < DS_MAX_CARDS; ++j) {
+            const int mu_j = __shfl(mu, j, DS_MAX_CARDS);
+            const int s_j = __shfl(slots, j, DS_MAX_CARDS);
+            const bool has = s_j > 0;
+            const bool first = has && (mu_j > mu || (mu_j == mu && j < k));
+            with_slots += has;
+            empty_below += !has && j < k;
+            earlier += first;
+            prefix += first ? s_j : 0;
+        }
+        const int rank = slots > 0 ? earlier : with_slots + empty_below;
+        long long t = (long long)cnt * count - prefix;
+        if (t > slots) t = slots;
+        const int take = t > 0 ? (int)t : 0;
+        if (take > 0)
+            card_apply(card_mem_used, card_cores_used, card_state, o, take,
+                       memory, cores, 1);
+        if (row)
+            assign[(size_t)e * K + rank] = take > 0
+                ? (int)(((unsigned)k << DS_TAKE_BITS) | (unsigned)take) : 0;
+    }
+}
+
+// Multi-class gang revert (beside cond_revert / spread_revert), gated on
+// the job flag: subtracts exactly what the assignment rows recorded and
+// zeroes them.  Same 16-lane groups; lane p owns position p of the row,
+// and the positions of a row name distinct cards.
+__global__ void __launch_bounds__(DS_THREADS) device_revert_kernel(
+    const uint8_t* __restrict__ flag, const int* __restrict__ log_nodes,
+    const int* __restrict__ log_len,
+    int* __restrict__ card_mem_used, int* __restrict__ card_cores_used,
+    int* __restrict__ card_state, int* __restrict__ assign,
+    int memory, int cores, int K, int N, int L)
+{
+    if (*flag) return;
+    int len = *log_len;
+    if (len > L) len = L;
+    const int p = threadIdx.x & (DS_MAX_CARDS - 1);
+    if (p >= K) return;
+    const int groups = gridDim.x * blockDim.x / DS_MAX_CARDS;
+    for (int e = (blockIdx.x * blockDim.x + threadIdx.x) / DS_MAX_CARDS;
+         e < len; e += groups) {
+        const unsigned v = (unsigned)assign[(size_t)e * K + p];
+        if (v == 0) continue;
+        assign[(size_t)e * K + p] = 0;
+        const int card = (int)(v >> DS_TAKE_BITS);
+        const int take = (int)(v & DS_TAKE_MASK);
+        const int node = log_nodes[e];
+        if (take == 0 || card >= K || node < 0 || node >= N) continue;
+        card_apply(card_mem_used, card_cores_used, card_state,
+                   (size_t)card * N + node, take, memory, cores, -1);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Megacycle: a WHOLE small-class plan in ONE launch.  Heterogeneous
 // inventories produce thousands of per-job classes; at ~2 enqueues per
 // class the cycle becomes launch-bound.  This kernel sequences the
@@ -1913,6 +2112,68 @@ void vamd_domain_count_add(
     hipLaunchKernelGGL(vamd::domain_count_add_kernel, dim3(blocks),
                        dim3(threads), 0, stream, log_nodes, log_counts,
                        log_len, dom_of, dom_count, D, N, K);
+}
+
+int vamd_device_max_cards(void) { return DS_MAX_CARDS; }
+
+// a request the kernels cannot divide by or index with launches nothing
+static bool device_shape_ok(int count, int memory, int cores, int K)
+{
+    return count >= 1 && memory >= 0 && cores >= 0 && K >= 1 &&
+        K <= DS_MAX_CARDS;
+}
+
+static int device_log_blocks(int L)
+{
+    const int per_block = DS_THREADS / DS_MAX_CARDS;
+    int blocks = min((L + per_block - 1) / per_block, 256);
+    return blocks < 1 ? 1 : blocks;
+}
+
+void vamd_device_cap(
+    float* score, int* cap, const int* card_mem_used,
+    const int* card_cores_used, const int* card_state,
+    const int* card_mem_total, int count, int memory, int cores, int K,
+    int N, hipStream_t stream)
+{
+    if (!device_shape_ok(count, memory, cores, K)) return;
+    int threads = 256;
+    int blocks = min((N + threads - 1) / threads, 4096);
+    if (blocks < 1) blocks = 1;
+#define VAMD_DEVICE_CAP(KB)                                                  \
+    hipLaunchKernelGGL(vamd::device_cap_kernel<KB>, dim3(blocks),            \
+                       dim3(threads), 0, stream, score, cap, card_mem_used,  \
+                       card_cores_used, card_state, card_mem_total, count,   \
+                       memory, cores, K, N)
+    if (K <= 4) VAMD_DEVICE_CAP(4);
+    else if (K <= 8) VAMD_DEVICE_CAP(8);
+    else VAMD_DEVICE_CAP(16);
+#undef VAMD_DEVICE_CAP
+}
+
+void vamd_device_commit(
+    const int* log_nodes, const int* log_counts, const int* log_len,
+    int* card_mem_used, int* card_cores_used, int* card_state,
+    const int* card_mem_total, int* assign, int count, int memory, int cores,
+    int K, int N, int L, hipStream_t stream)
+{
+    if (!device_shape_ok(count, memory, cores, K)) return;
+    hipLaunchKernelGGL(vamd::device_commit_kernel, dim3(device_log_blocks(L)),
+                       dim3(DS_THREADS), 0, stream, log_nodes, log_counts,
+                       log_len, card_mem_used, card_cores_used, card_state,
+                       card_mem_total, assign, count, memory, cores, K, N, L);
+}
+
+void vamd_device_revert(
+    const uint8_t* flag, const int* log_nodes, const int* log_len,
+    int* card_mem_used, int* card_cores_used, int* card_state, int* assign,
+    int memory, int cores, int K, int N, int L, hipStream_t stream)
+{
+    if (!device_shape_ok(1, memory, cores, K)) return;
+    hipLaunchKernelGGL(vamd::device_revert_kernel, dim3(device_log_blocks(L)),
+                       dim3(DS_THREADS), 0, stream, flag, log_nodes, log_len,
+                       card_mem_used, card_cores_used, card_state, assign,
+                       memory, cores, K, N, L);
 }
 
 void vamd_batch_score(const VamdCycle& cy, const VamdDevDescs& dd, int c0,

@@ -106,6 +106,49 @@ void vamd_domain_count_add(
     const int* dom_of, int* dom_count, int D, int N, int K,
     hipStream_t stream);
 
+// --- device share: per-card packing of GPU slices --------------------------
+//
+// Card planes are int32 [K, N] (card-major), K <= vamd_device_max_cards():
+// card_mem_used, card_cores_used (percent) and card_state = slice count,
+// with VAMD_CARD_GONE set for an exclusive or absent card;
+// card_mem_total[N] < 2^28.  A request is (count slices, memory per slice,
+// cores per slice); memory == 0 && cores == 0 asks for whole cards.  The
+// rule is GPUDevicePool.allocate once per pod (best fit: fullest feasible
+// card first, ties to the lower index), computed in closed form.
+//
+// The three launchers are weak: a program that links the runner alone
+// (the dispatch trace) never sets the device-share block and never calls
+// them.
+#define VAMD_CARD_GONE (1 << 30)
+
+// After vamd_score_cap, before any domain rule: cap = min(cap, S / count)
+// with S the node's slots for the shape; score = -inf where that is 0.
+__attribute__((weak)) void vamd_device_cap(
+    float* score, int* cap, const int* card_mem_used,
+    const int* card_cores_used, const int* card_state,
+    const int* card_mem_total, int count, int memory, int cores, int K,
+    int N, hipStream_t stream);
+
+// After the select: entry e < *log_len (<= L) of the log takes
+// log_counts[e] * count slices on node log_nodes[e], cards in the order
+// (mem_used desc, index asc) among cards with slots.  assign[L, K]: the
+// used cards of entry e in that order, card << 28 | take; the tail is 0.
+__attribute__((weak)) void vamd_device_commit(
+    const int* log_nodes, const int* log_counts, const int* log_len,
+    int* card_mem_used, int* card_cores_used, int* card_state,
+    const int* card_mem_total, int* assign, int count, int memory, int cores,
+    int K, int N, int L, hipStream_t stream);
+
+// When *flag == 0: gives back what the assignment rows recorded and zeroes
+// them (beside vamd_cond_revert / vamd_spread_revert).
+__attribute__((weak)) void vamd_device_revert(
+    const uint8_t* flag, const int* log_nodes, const int* log_len,
+    int* card_mem_used, int* card_cores_used, int* card_state, int* assign,
+    int memory, int cores, int K, int N, int L, hipStream_t stream);
+
+// Largest K of the card planes.
+__attribute__((weak)) int vamd_device_max_cards(void);
+
 // --- whole-cycle runner ----------------------------------------------------
 
 // One task class (a batch of identical pending tasks of one job).
@@ -209,6 +252,16 @@ struct VamdCycle {
     const int32_t* domains;        // HOST [G]: D of each group
     void* domain_scratch;          // 12*N bytes, 8-aligned
     const int32_t* group_row;      // HOST [G]: row of dom_of for group g; null = g
+    // device-share block: live only when all of it is set (card_K >= 1)
+    int32_t* card_mem_used;        // [card_K, N]
+    int32_t* card_cores_used;      // [card_K, N]
+    int32_t* card_state;           // [card_K, N]
+    const int32_t* card_mem_total; // [N]
+    const int32_t* class_dev_req;  // HOST [C, 4]: count, memory, cores, 0;
+                                   //   count == 0 = no device request
+    int32_t* dev_assign;           // [L, card_K], parallel to the log
+    int32_t card_K;
+    int32_t _pad2;
 };
 
 // Device copies of the descriptor arrays (chain and megacycle paths).
@@ -258,6 +311,13 @@ void vamd_megacycle(const VamdCycle& cy, const VamdDevDescs& dd,
 //     share one leaf_of row through group_row.
 //   * With the domain block dead (or every group -1) nothing above
 //     changes a single launch.
+//   * A class with a device request (device-share block live,
+//     class_dev_req[c].count > 0) always takes the split path:
+//     vamd_score_cap -> vamd_device_cap -> [its domain rule] -> select
+//     (bulk by size) -> [count update] -> vamd_device_commit — never the
+//     fused, chain or megacycle path — and its multi-class revert runs
+//     vamd_device_revert beside the existing one.  With the block dead
+//     nothing changes a single launch.
 // Returns 0; nonzero, before any HIP call, when cy->struct_size is not
 // sizeof(VamdCycle).
 int vamd_run_cycle(const VamdCycle* cy, hipStream_t stream);

@@ -16,7 +16,8 @@ from typing import Optional
 import torch
 
 from .build import LIB_PATH, build
-from .reference import check_hypernode_table
+from .reference import (DEV_MAX_CARDS, check_device_request,
+                        check_hypernode_table)
 
 _lib = None
 
@@ -57,7 +58,10 @@ class VamdCycle(Structure):
         "score_scratch", "cap_scratch", "log_nodes", "log_counts", "log_len",
         "class_placed", "job_placed", "job_flag", "sort_scratch",
         "class_group", "class_skew", "class_mode", "dom_of", "count",
-        "count_off", "domains", "domain_scratch", "group_row")]
+        "count_off", "domains", "domain_scratch", "group_row",
+        "card_mem_used", "card_cores_used", "card_state", "card_mem_total",
+        "class_dev_req", "dev_assign")] + [
+        ("card_K", c_int32), ("_pad2", c_int32)]
 
 
 def _load():
@@ -90,6 +94,14 @@ def _load():
         raise RuntimeError(
             "the loaded kernel library and this module disagree on "
             "HYPERNODE_LDS_LEAVES; rebuild (python -m volcano_amd.ops.build)")
+    lib.vamd_device_cap.restype = None
+    lib.vamd_device_commit.restype = None
+    lib.vamd_device_revert.restype = None
+    lib.vamd_device_max_cards.restype = c_int
+    if lib.vamd_device_max_cards() != DEV_MAX_CARDS:
+        raise RuntimeError(
+            "the loaded kernel library and this module disagree on "
+            "DEV_MAX_CARDS; rebuild (python -m volcano_amd.ops.build)")
     _lib = lib
     return lib
 
@@ -287,6 +299,76 @@ def domain_count_add(log_nodes, log_counts, log_len, dom_of, dom_count):
         _p(dom_count), c_int(D), c_int(N), c_int(K), _stream())
 
 
+def _card_planes(op, mem_used, cores_used, state, mem_total):
+    """(K, N) of a set of card planes, checked."""
+    if mem_used.dim() != 2 or not 1 <= mem_used.shape[0] <= DEV_MAX_CARDS:
+        raise ValueError(f"{op}: card planes are [K, N], "
+                         f"1 <= K <= {DEV_MAX_CARDS}")
+    K, N = mem_used.shape
+    if cores_used.shape != (K, N) or state.shape != (K, N) \
+            or mem_total.shape != (N,):
+        raise ValueError(f"{op}: card planes differ in shape")
+    for t in (mem_used, cores_used, state, mem_total):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError(f"{op}: card planes are contiguous int32")
+    return K, N
+
+
+def device_cap(score, cap, mem_used, cores_used, state, mem_total, request):
+    """Per-card packing clamp (after score_cap, before any domain rule):
+    ``cap = min(cap, S // count)`` with ``S`` the node's slots for
+    ``request`` = (count, memory, cores) on the card planes [K, N];
+    ``score = -inf`` where that leaves 0.  Both change in place."""
+    lib = _load()
+    count, memory, cores = check_device_request(request)
+    K, N = _card_planes("device_cap", mem_used, cores_used, state, mem_total)
+    if score.shape != (N,) or cap.shape != (N,):
+        raise ValueError("device_cap: score and cap need one entry per node")
+    lib.vamd_device_cap(
+        _p(score), _p(cap), _p(mem_used), _p(cores_used), _p(state),
+        _p(mem_total), c_int(count), c_int(memory), c_int(cores), c_int(K),
+        c_int(N), _stream())
+
+
+def device_commit(log_nodes, log_counts, log_len, mem_used, cores_used, state,
+                  mem_total, assign, request):
+    """The logged placements take their slices on the card planes (after
+    the select); ``assign`` [L, K] int32 receives, per log entry, the used
+    cards in fill order as ``card << 28 | take``."""
+    lib = _load()
+    count, memory, cores = check_device_request(request)
+    K, N = _card_planes("device_commit", mem_used, cores_used, state,
+                        mem_total)
+    L = log_nodes.shape[0]
+    if log_counts.shape[0] != L or assign.shape != (L, K) \
+            or assign.dtype != torch.int32 or not assign.is_contiguous():
+        raise ValueError("device_commit: assign is contiguous int32 [L, K], "
+                         "parallel to the log")
+    lib.vamd_device_commit(
+        _p(log_nodes), _p(log_counts), _p(log_len), _p(mem_used),
+        _p(cores_used), _p(state), _p(mem_total), _p(assign), c_int(count),
+        c_int(memory), c_int(cores), c_int(K), c_int(N), c_int(L), _stream())
+
+
+def device_revert(flag, log_nodes, log_len, mem_used, cores_used, state,
+                  mem_total, assign, request):
+    """When ``flag`` is 0: the card planes give back what ``assign``
+    recorded, and ``assign`` is zeroed."""
+    lib = _load()
+    _, memory, cores = check_device_request(request)
+    K, N = _card_planes("device_revert", mem_used, cores_used, state,
+                        mem_total)
+    L = log_nodes.shape[0]
+    if assign.shape != (L, K) or assign.dtype != torch.int32 \
+            or not assign.is_contiguous():
+        raise ValueError("device_revert: assign is contiguous int32 [L, K], "
+                         "parallel to the log")
+    lib.vamd_device_revert(
+        _p(flag), _p(log_nodes), _p(log_len), _p(mem_used), _p(cores_used),
+        _p(state), _p(assign), c_int(memory), c_int(cores), c_int(K),
+        c_int(N), c_int(L), _stream())
+
+
 def fused_score_select(alloc_t, used_t, extra_t, ready, taints, planes_t,
                        req, tolerated, require, forbid, w_least, w_most,
                        w_bal, dim_w, bias, score, cap, ntasks,
@@ -326,7 +408,7 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
               class_forbid, class_min, dim_w, queue_alloc, queue_limit,
               score_scratch, cap_scratch, log_nodes, log_counts, log_len,
               class_placed, job_placed, job_flag, sort_scratch=None,
-              spread=None):
+              spread=None, devices=None):
     """One library call = one whole allocate cycle (plan built host-side).
 
     ``class_descs`` / ``job_descs`` are host buffers of ``VamdClassDesc`` /
@@ -343,7 +425,13 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
     a spread class.  An optional ``group_row`` (host int32 numpy [G]) names
     the row of ``dom_of`` each group reads — all network-topology groups
     share one ``leaf_of`` row; without it group g reads row g.  The
-    ``count`` slice of a mode-3 group is its table."""
+    ``count`` slice of a mode-3 group is its table.
+
+    ``devices`` (plans with device-request classes only) is a dict: the
+    card planes ``mem_used``/``cores_used``/``state`` device i32 [K, N],
+    ``mem_total`` device i32 [N], ``class_req`` host int32 numpy [C, 4]
+    (count, memory, cores, 0; count 0 = no request) and ``assign`` device
+    i32 [L, K] (zeroed), parallel to the log."""
     lib = _load()
     R, N = alloc_t.shape
     cy = VamdCycle(
@@ -382,6 +470,26 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
                     rows.shape[0] != spread["domains"].shape[0]:
                 raise ValueError("run_cycle: group_row must be int32 [G]")
             cy.group_row = rows.ctypes.data
+    if devices is not None:
+        K, _ = _card_planes("run_cycle", devices["mem_used"],
+                            devices["cores_used"], devices["state"],
+                            devices["mem_total"])
+        creq = devices["class_req"]
+        if creq.shape != (n_classes, 4) or creq.dtype != "int32" \
+                or not creq.flags["C_CONTIGUOUS"]:
+            raise ValueError("run_cycle: devices.class_req must be int32 "
+                             "[C, 4]")
+        for row in creq[creq[:, 0] > 0]:
+            check_device_request(row[:3])
+        if devices["assign"].shape != (log_nodes.shape[0], K):
+            raise ValueError("run_cycle: devices.assign must be [L, K]")
+        cy.card_mem_used = _addr(devices["mem_used"])
+        cy.card_cores_used = _addr(devices["cores_used"])
+        cy.card_state = _addr(devices["state"])
+        cy.card_mem_total = _addr(devices["mem_total"])
+        cy.class_dev_req = creq.ctypes.data
+        cy.dev_assign = _addr(devices["assign"])
+        cy.card_K = K
     rc = lib.vamd_run_cycle(ctypes.byref(cy), _stream())
     if rc != 0:
         raise RuntimeError(

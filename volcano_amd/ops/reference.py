@@ -530,6 +530,207 @@ def hypernode_mask(
     cap[out] = 0
 
 
+# -- device share: per-card packing of GPU slices ---------------------------
+#
+# Card planes are CPU int32 tensors [K, N]: ``mem_used``, ``cores_used`` and
+# ``state`` (slice count, DEV_GONE set for an exclusive or absent card),
+# plus ``mem_total`` [N].  A request is (count, memory, cores).  The oracles
+# are the plain per-pod loop over ``GPUDevicePool`` — the sequential host
+# rule itself; the ``*_closed`` twins are the closed form the HIP kernels
+# compute (one array pass, no per-pod step).
+
+DEV_GONE = 1 << 30              # card_state bit: exclusive or absent
+DEV_MAX_CARDS = 16              # K of the card planes
+DEV_MEM_LIMIT = 1 << 28         # mem_total (and a slice) stays below this
+DEV_TAKE_BITS = 28              # assignment word: card << 28 | take
+
+
+def check_device_request(request):
+    """(count, memory, cores) as ints, or ValueError."""
+    count, memory, cores = (int(x) for x in request)
+    if count < 1 or not 0 <= memory < DEV_MEM_LIMIT or not 0 <= cores <= 100:
+        raise ValueError(
+            f"device request {(count, memory, cores)}: count >= 1, "
+            f"0 <= memory < 2^28, 0 <= cores <= 100")
+    return count, memory, cores
+
+
+def _device_pool(mem_used, cores_used, state, mem_total, n):
+    """Node n's cards as a GPUDevicePool (an absent card can never be
+    taken, like an exclusive one)."""
+    from ..api.devices import Card, GPUDevicePool
+    pool = GPUDevicePool.__new__(GPUDevicePool)
+    pool.cards = [
+        Card(k, int(mem_total[n]), int(mem_used[k, n]), int(cores_used[k, n]),
+             bool(int(state[k, n]) & DEV_GONE), int(state[k, n]) & ~DEV_GONE)
+        for k in range(mem_used.shape[0])]
+    return pool
+
+
+def _card_arrays(mem_used, cores_used, state, mem_total):
+    for t in (mem_used, cores_used, state, mem_total):
+        if t.device.type != "cpu" or t.dtype != torch.int32:
+            raise ValueError("device oracles take CPU int32 card planes")
+    return (mem_used.numpy(), cores_used.numpy(), state.numpy(),
+            mem_total.numpy())
+
+
+def device_cap(score, cap, mem_used, cores_used, state, mem_total,
+               request) -> None:
+    """``cap[n] = min(cap[n], pods GPUDevicePool.allocate packs in a row)``,
+    ``score[n] = -inf`` where that is 0 — the oracle of the HIP
+    ``device_cap``."""
+    from ..api.devices import DeviceRequest
+    req = DeviceRequest(*check_device_request(request))
+    mu, cu, st, total = _card_arrays(mem_used, cores_used, state, mem_total)
+    cap_h = cap.cpu()
+    for n in torch.nonzero(cap_h > 0).flatten().tolist():
+        pool = _device_pool(mu, cu, st, total, n)
+        fit = 0
+        while fit < int(cap_h[n]) and pool.allocate(req) is not None:
+            fit += 1
+        if fit < int(cap_h[n]):
+            cap[n] = fit
+            if fit == 0:
+                score[n] = NEG_INF
+
+
+def device_commit(log_nodes, log_counts, log_len, mem_used, cores_used,
+                  state, mem_total, assign, request) -> None:
+    """Every logged pod takes its slices through ``GPUDevicePool.allocate``,
+    one pod at a time; ``assign`` [L, K] (CPU int32) records, per entry, the
+    run-length form of the picked cards: ``card << 28 | take`` in pick
+    order, then zeros — the oracle of the HIP ``device_commit``."""
+    from ..api.devices import DeviceRequest
+    req = DeviceRequest(*check_device_request(request))
+    mu, cu, st, total = _card_arrays(mem_used, cores_used, state, mem_total)
+    rows = assign.numpy().view("uint32")
+    nodes, counts = log_nodes.cpu().tolist(), log_counts.cpu().tolist()
+    for e in range(min(int(log_len), len(nodes))):
+        rows[e] = 0
+        if counts[e] <= 0:
+            continue
+        n = nodes[e]
+        pool = _device_pool(mu, cu, st, total, n)
+        runs = []                           # [card, take] in pick order
+        for _ in range(counts[e]):
+            picked = pool.allocate(req)
+            if picked is None:
+                raise RuntimeError(f"device_commit: node {n} cannot pack "
+                                   f"{counts[e]} pods of {request}")
+            for k in picked:
+                if runs and runs[-1][0] == k:
+                    runs[-1][1] += 1
+                else:
+                    runs.append([k, 1])
+        for p, (k, take) in enumerate(runs):
+            rows[e, p] = (k << DEV_TAKE_BITS) | take
+        for c in pool.cards:
+            mu[c.index, n], cu[c.index, n] = c.mem_used, c.cores_used
+            st[c.index, n] = c.slices | (DEV_GONE if c.exclusive else 0)
+
+
+def device_revert(flag, log_nodes, log_len, mem_used, cores_used, state,
+                  mem_total, assign, request) -> None:
+    """When ``flag`` is 0 the cards release what ``assign`` recorded
+    (``Card.release`` per slice) and ``assign`` is zeroed."""
+    from ..api.devices import DeviceRequest
+    if int(flag) != 0:
+        return
+    req = DeviceRequest(*check_device_request(request))
+    mu, cu, st, total = _card_arrays(mem_used, cores_used, state, mem_total)
+    rows = assign.numpy().view("uint32")
+    nodes = log_nodes.cpu().tolist()
+    for e in range(min(int(log_len), len(nodes))):
+        n = nodes[e]
+        pool = _device_pool(mu, cu, st, total, n)
+        for word in rows[e].tolist():
+            c = pool.cards[word >> DEV_TAKE_BITS]
+            for _ in range(word & ((1 << DEV_TAKE_BITS) - 1)):
+                c.release(req)
+            mu[c.index, n], cu[c.index, n] = c.mem_used, c.cores_used
+            st[c.index, n] = c.slices | (DEV_GONE if c.exclusive else 0)
+        rows[e] = 0
+
+
+def device_slots(mem_used, cores_used, state, mem_total, request):
+    """Closed form, fact 1: slots per card [K, N] (int64 numpy) — how many
+    slices of the shape each card still takes; a node packs exactly
+    ``slots.sum(0) // count`` pods, whatever the order."""
+    import numpy as np
+    count, memory, cores = check_device_request(request)
+    mu, cu, st, total = (a.astype(np.int64) for a in _card_arrays(
+        mem_used, cores_used, state, mem_total))
+    gone = (st & DEV_GONE) != 0
+    if memory == 0 and cores == 0:
+        return np.where(~gone & (st == 0), 1, 0).astype(np.int64)
+    s = np.full(mu.shape, np.iinfo(np.int64).max)
+    if memory > 0:
+        s = np.minimum(s, np.floor_divide(total[None, :] - mu, memory))
+    if cores > 0:
+        s = np.minimum(s, np.floor_divide(100 - cu, cores))
+    return np.where(gone | (mu > total[None, :]), 0, np.maximum(s, 0))
+
+
+def device_cap_closed(score, cap, mem_used, cores_used, state, mem_total,
+                      request) -> None:
+    """``device_cap`` in closed form (what the HIP kernel computes)."""
+    import numpy as np
+    fit = device_slots(mem_used, cores_used, state, mem_total,
+                       request).sum(0) // int(request[0])
+    cap_h = cap.cpu().numpy().astype(np.int64)
+    hit = torch.from_numpy((cap_h > 0) & (fit < cap_h))
+    cap[hit] = torch.from_numpy(fit.astype(np.int32))[hit]
+    score[hit & torch.from_numpy(fit == 0)] = NEG_INF
+
+
+def device_commit_closed(log_nodes, log_counts, log_len, mem_used,
+                         cores_used, state, mem_total, assign,
+                         request) -> None:
+    """``device_commit`` in closed form, fact 2: the cards of a node fill
+    in the order (mem_used desc, index asc) among cards with slots, each to
+    its slot count; card k takes ``clamp(cnt*count - prefix_k, 0,
+    slots_k)`` with ``prefix_k`` the slots ranked before it."""
+    import numpy as np
+    count, memory, cores = check_device_request(request)
+    slots = device_slots(mem_used, cores_used, state, mem_total, request)
+    mu, cu, st, _ = _card_arrays(mem_used, cores_used, state, mem_total)
+    rows = assign.numpy().view("uint32")
+    K = mu.shape[0]
+    nodes, counts = log_nodes.cpu().tolist(), log_counts.cpu().tolist()
+    for e in range(min(int(log_len), len(nodes))):
+        rows[e] = 0
+        if counts[e] <= 0:
+            continue
+        n = nodes[e]
+        s = slots[:, n]
+        order = sorted((k for k in range(K) if s[k] > 0),
+                       key=lambda k: (-int(mu[k, n]), k))
+        prefix = 0
+        for p, k in enumerate(order):
+            take = int(min(max(counts[e] * count - prefix, 0), s[k]))
+            prefix += int(s[k])
+            if take == 0:
+                break
+            rows[e, p] = (k << DEV_TAKE_BITS) | take
+            if memory == 0 and cores == 0:
+                st[k, n] = (int(st[k, n]) + take) | DEV_GONE
+            else:
+                st[k, n] += take
+                mu[k, n] += take * memory
+                cu[k, n] += take * cores
+
+
+def device_cards(row, cnt: int, count: int):
+    """One card list per pod from an assignment row: the row spells the
+    slice sequence, pod i owns positions [i*count, (i+1)*count)."""
+    seq = []
+    for word in (int(w) & 0xFFFFFFFF for w in row):
+        seq.extend([word >> DEV_TAKE_BITS]
+                   * (word & ((1 << DEV_TAKE_BITS) - 1)))
+    return [seq[i * count:(i + 1) * count] for i in range(cnt)]
+
+
 def drf_share(job_alloc: torch.Tensor, total: torch.Tensor) -> torch.Tensor:
     """Dominant share per job: max_r alloc/total (drf.go calculateShare).
 

@@ -306,6 +306,42 @@ class AllocateAction:
                     tiers, max(1, int(need)), hypernode_exact.n_leaves,
                     pin, soft))
 
+        # exact device share (deviceshare plugin, ``exact: true``): a class
+        # with a device request is packed per card on the device, per
+        # placement.  Not under the soft-shard coordinator, which keeps the
+        # host bit.
+        device_exact = getattr(ssn, "device_exact", None) \
+            if self.coordinator is None else None
+
+        def device_attach(cp: ClassPlan) -> None:
+            """Attach cp's device request, if it has one; its constraint
+            words lose the session-open ``dev-unfit:`` bit (copy first, the
+            memoized arrays are shared)."""
+            if device_exact is None:
+                return
+            rq = device_exact.request_of(cp.tclass.tasks[0])
+            if rq is None:
+                return
+            if plan.device_state is None:
+                plan.set_device_state(*device_exact.planes)
+            plan.add_device_request(cp, *rq.signature())
+            bit = device_exact.unfit_bits.get(rq.signature())
+            if bit is not None and bit // 64 < len(cp.forbid):
+                cp.forbid = cp.forbid.copy()
+                cp.forbid[bit // 64] &= ~(np.int64(1) << np.int64(bit % 64))
+
+        def device_job(jb) -> bool:
+            t0_ = next(iter(jb.task_status_index.get(
+                _TS.PENDING, {}).values()), None)
+            return t0_ is not None and \
+                device_exact.request_of(t0_) is not None
+
+        # such jobs never join a fused signature run
+        if device_exact is not None and elig_l is not None:
+            for ix, jb in enumerate(jobs_l):
+                if elig_l[ix] and device_job(jb):
+                    elig_l[ix] = False
+
         if hypernode_exact is not None and elig_l is not None:
             # each such job needs its own domain: none joins a fused run
             for ix, jb in enumerate(jobs_l):
@@ -456,8 +492,10 @@ class AllocateAction:
                 hn = hypernode_exact.resolve_job(job) \
                     if hypernode_exact is not None and sp is None \
                     and af is None else None
+                dv = device_exact.request_of(first) \
+                    if device_exact is not None else None
                 if sp is None and af is None and hn is None \
-                        and not bias_fns \
+                        and dv is None and not bias_fns \
                         and open_bundle is not None \
                         and open_key == (qi, sig):
                     tasks = list(pend.values())
@@ -521,10 +559,13 @@ class AllocateAction:
                     affinity_attach(cp, af)
                 elif hn is not None:
                     hypernode_attach(cp, job, hn, gang_min)
-                # biased and domain-rule classes never fuse
+                if dv is not None:
+                    device_attach(cp)
+                # biased, domain-rule and device classes never fuse
                 if cp.bias is not None or cp.spread is not None \
                         or cp.affinity is not None \
-                        or cp.hypernode is not None:
+                        or cp.hypernode is not None \
+                        or cp.device is not None:
                     close_bundle()
                     plan.add_job(job, [cp])
                 else:
@@ -577,6 +618,7 @@ class AllocateAction:
                     af = affinity_exact.resolve_task(tc.tasks[0])
                     if af is not None:
                         affinity_attach(cp, af)
+                device_attach(cp)
                 classes.append(cp)
             if skipped and classes and job.min_available > sum(
                     c.tclass.count for c in classes) + job.occupied_count:
@@ -595,7 +637,8 @@ class AllocateAction:
                           and classes[0].bias is None
                           and classes[0].spread is None
                           and classes[0].affinity is None
-                          and classes[0].hypernode is None)
+                          and classes[0].hypernode is None
+                          and classes[0].device is None)
             if bundleable:
                 cp = classes[0]
                 gang_min = max(job.min_available, cp.min_needed)
@@ -619,6 +662,18 @@ class AllocateAction:
         bad = frozenset()
         if coord is not None:
             bad = coord.find_conflicts(nt, used_before)
+        if result is not None and device_exact is not None:
+            # The cards the cycle chose, for the plugin's on_allocate, keyed
+            # by the class object the event carries.  Two invariants make
+            # the hand-off line up: (1) a device class never bundles, so the
+            # walk fires on_allocate at most ONCE per tclass, with all of
+            # its pieces; (2) the walk and class_cards both skip exactly
+            # the log entries with count <= 0 and keep log order, so the
+            # i-th card list belongs to the i-th task of the event.
+            device_exact.cards = {
+                id(cp.tclass): result.class_cards(c)
+                for c, cp in enumerate(plan.classes)
+                if cp.device is not None}
         if result is not None:
             self._gate_subgroup_families(plan, result)
             self._apply(ssn, plan, result, bad_nodes=bad)

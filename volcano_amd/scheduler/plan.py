@@ -71,6 +71,20 @@ class SpreadGroup:
 
 
 @dataclass(slots=True)
+class DeviceState:
+    """Per-card state of the inventory at cycle start (deviceshare with
+    ``exact: true``): int32 card planes ``[K, N]``, K <= 16, laid out like
+    the resource planes.  ``state`` is the slice count with
+    ``ref.DEV_GONE`` set for an exclusive card and for the missing cards of
+    a node with fewer than K.  The runners keep the live planes for the
+    whole cycle; the host pools stay the ledger across cycles."""
+    mem_used: np.ndarray       # [K, N] i32
+    cores_used: np.ndarray     # [K, N] i32, percent
+    state: np.ndarray          # [K, N] i32
+    mem_total: np.ndarray      # [N] i32, < 2^28
+
+
+@dataclass(slots=True)
 class ClassPlan:
     tclass: TaskClass
     job_key: str
@@ -114,6 +128,11 @@ class ClassPlan:
     # chosen on the device from the live cap.  Never combined with
     # ``bundle``, ``spread`` or ``affinity``.
     hypernode: Optional[int] = None
+    # device request (count, memory, cores) packed per card on the device
+    # (CyclePlan.add_device_request): device_cap after the score, the
+    # slices taken by device_commit after the select.  Composes with every
+    # domain rule; never combined with ``bundle``.
+    device: Optional[Tuple[int, int, int]] = None
 
     @property
     def ntasks(self) -> int:
@@ -143,8 +162,9 @@ class CycleResult:
     cold consumers (subgroup gating, tests)."""
 
     def __init__(self, plan, log_nodes, log_counts, log_len, class_placed,
-                 job_placed, job_flag):
+                 job_placed, job_flag, dev_assign=None):
         self.plan = plan
+        self.dev_assign = dev_assign       # [L, K] i32, or None
         self.log_nodes = log_nodes
         self.log_counts = log_counts
         self.log_len = log_len
@@ -172,6 +192,20 @@ class CycleResult:
         n = int(self.log_len[c])
         sl = slice(cp.log_off, cp.log_off + n)
         return self.log_nodes[sl], self.log_counts[sl]
+
+    def class_cards(self, c: int) -> List[List[int]]:
+        """Card indices of every placed task of device class c, one list
+        per task, in log order (entry by entry, ``count`` slices each)."""
+        cp = self.plan.classes[c]
+        if cp.device is None or self.dev_assign is None:
+            return []
+        _, lc = self.class_entries(c)
+        out: List[List[int]] = []
+        for e, cnt in enumerate(lc.tolist()):
+            if cnt > 0:
+                out.extend(ref.device_cards(self.dev_assign[cp.log_off + e],
+                                            cnt, cp.device[0]))
+        return out
 
     @property
     def class_results(self) -> List[ClassResult]:
@@ -207,6 +241,37 @@ class CyclePlan:
         # groups, and the groups already made per (row, table)
         self.hypernode_rows: List[Tuple[np.ndarray, int]] = []
         self._hypernode_groups: Dict[Tuple[int, bytes], int] = {}
+        # card planes at cycle start, and the live planes of the last run
+        # (tensors on the runner's side, left for inspection)
+        self.device_state: Optional[DeviceState] = None
+        self.device_planes = None
+
+    def set_device_state(self, mem_used, cores_used, state,
+                         mem_total) -> None:
+        """The inventory's card planes ([K, N] / [N] int32)."""
+        planes = [np.ascontiguousarray(a, dtype=np.int32)
+                  for a in (mem_used, cores_used, state)]
+        mem_total = np.ascontiguousarray(mem_total, dtype=np.int32)
+        K = planes[0].shape[0] if planes[0].ndim == 2 else 0
+        if not 1 <= K <= ref.DEV_MAX_CARDS or \
+                any(a.shape != (K, self.nt.n) for a in planes) or \
+                mem_total.shape != (self.nt.n,):
+            raise ValueError("device state: card planes are [K, N] with "
+                             f"1 <= K <= {ref.DEV_MAX_CARDS}, mem_total [N]")
+        if mem_total.max(initial=0) >= ref.DEV_MEM_LIMIT or \
+                mem_total.min(initial=0) < 0:
+            raise ValueError("device state: mem_total outside [0, 2^28)")
+        self.device_state = DeviceState(*planes, mem_total)
+
+    def add_device_request(self, cp: ClassPlan, count: int, memory: int,
+                           cores: int) -> None:
+        """Pack cp's instances per card: ``count`` slices of (memory,
+        cores) each; memory == cores == 0 asks for whole cards."""
+        if self.device_state is None:
+            raise ValueError("device request without device state")
+        if cp.bundle is not None:
+            raise ValueError("device classes never bundle")
+        cp.device = ref.check_device_request((count, memory, cores))
 
     def add_hypernode_row(self, leaf_of, n_leaves: int) -> int:
         """Register a node → leaf map (leaves numbered depth-first over
@@ -332,6 +397,10 @@ class CyclePlan:
                                      "bundle")
                 if cp.spread is not None or cp.affinity is not None:
                     raise ValueError(f"class {c}: one domain rule per class")
+            if cp.device is not None and (cp.bundle is not None or
+                                          self.device_state is None):
+                raise ValueError(f"class {c}: a device class needs device "
+                                 "state and never bundles")
             for rule in (cp.spread, cp.affinity):
                 if rule is not None and self.spread_groups[rule[0]].row >= 0:
                     raise ValueError(f"class {c}: group {rule[0]} is a "
@@ -379,8 +448,22 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
     sp_cnt = [torch.from_numpy(g.count.copy()).to(dev)
               for g in plan.spread_groups]
     plan.spread_counts = sp_cnt
+    # card planes and assignment rows live on the host here: the device
+    # oracles are the per-pod GPUDevicePool loop
+    cards = dev_assign = None
+    if any(cp.device is not None for cp in plan.classes):
+        ds = plan.device_state
+        cards = [torch.from_numpy(a.copy()) for a in
+                 (ds.mem_used, ds.cores_used, ds.state, ds.mem_total)]
+        dev_assign = torch.zeros((plan.log_total, cards[0].shape[0]),
+                                 dtype=torch.int32)
+        plan.device_planes = dict(zip(
+            ("mem_used", "cores_used", "state", "mem_total"), cards))
 
     def revert(c, cp, flag, req, sl):
+        if cp.device is not None:
+            ref.device_revert(flag, log_nodes[sl], log_len[c], *cards,
+                              dev_assign[sl], cp.device)
         if cp.spread is not None or cp.affinity is not None:
             g = (cp.spread or cp.affinity)[0]
             ref.spread_revert(flag, log_nodes[sl], log_counts[sl],
@@ -409,6 +492,8 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
                           planes, req, cp.tolerated, require, forbid,
                           cp.w_least, cp.w_most, cp.w_bal, dim_w, b,
                           score, cap)
+            if cp.device is not None:
+                ref.device_cap(score, cap, *cards, cp.device)
             sl = slice(cp.log_off, cp.log_off + cp.log_cap)
             if single:
                 # a discarded single-class gang leaves no trace (the HIP
@@ -458,6 +543,10 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
                     idx = log_nodes[sl][:int(log_len[c])].long()
                     used[idx] = used_before[idx]
                     plan.queue_alloc[cp.queue_idx].copy_(qa_before)
+            # the (zeroed) log of a discarded single-class gang takes nothing
+            if cp.device is not None:
+                ref.device_commit(log_nodes[sl], log_counts[sl], log_len[c],
+                                  *cards, dev_assign[sl], cp.device)
         if not single:
             ref.finalize_job(job_placed[j], jp.occupied, jp.min_available,
                              class_placed[jp.class_begin:jp.class_end],
@@ -472,7 +561,8 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
     return CycleResult(plan, log_nodes.cpu().numpy(),
                       log_counts.cpu().numpy(), log_len.cpu().numpy(),
                       class_placed.cpu().numpy(), job_placed.cpu().numpy(),
-                      job_flag.cpu().numpy())
+                      job_flag.cpu().numpy(),
+                      None if dev_assign is None else dev_assign.numpy())
 
 
 def run_plan_hip(plan: CyclePlan) -> CycleResult:
@@ -618,6 +708,27 @@ def run_plan_hip(plan: CyclePlan) -> CycleResult:
         plan.spread_counts = [count[int(o):int(o) + int(d)]
                               for o, d in zip(offs, lens)]
 
+    # device-request classes: the card planes go up once, the per-class
+    # request column stays host-side for the runner, and the assignment
+    # rows (parallel to the log) come back with the log
+    devices = None
+    if any(cp.device is not None for cp in plan.classes):
+        ds = plan.device_state
+        creq = np.zeros((C, 4), dtype=np.int32)
+        for c, cp in enumerate(plan.classes):
+            if cp.device is not None:
+                creq[c, :3] = cp.device
+        devices = dict(
+            mem_used=torch.from_numpy(ds.mem_used).to(dev),
+            cores_used=torch.from_numpy(ds.cores_used).to(dev),
+            state=torch.from_numpy(ds.state).to(dev),
+            mem_total=torch.from_numpy(ds.mem_total).to(dev),
+            class_req=creq,
+            assign=torch.zeros((plan.log_total, ds.mem_used.shape[0]),
+                               dtype=torch.int32, device=dev))
+        plan.device_planes = {k: devices[k] for k in (
+            "mem_used", "cores_used", "state", "mem_total")}
+
     hip.run_cycle(
         ctypes.c_void_p(cds.ctypes.data), C,
         ctypes.c_void_p(jds.ctypes.data), len(plan.jobs),
@@ -625,12 +736,14 @@ def run_plan_hip(plan: CyclePlan) -> CycleResult:
         nt.planes_t, bias, bias_rows, class_req, class_tol, class_require,
         class_forbid, class_min, dim_w, q_alloc, q_limit, score, cap,
         log_nodes, log_counts, log_len, class_placed, job_placed, job_flag,
-        sort_scratch, spread=spread)
+        sort_scratch, spread=spread, devices=devices)
 
     res = CycleResult(plan, log_nodes.cpu().numpy(),
                       log_counts.cpu().numpy(), log_len.cpu().numpy(),
                       class_placed.cpu().numpy(), job_placed.cpu().numpy(),
-                      job_flag.cpu().numpy())
+                      job_flag.cpu().numpy(),
+                      None if devices is None
+                      else devices["assign"].cpu().numpy())
     # the cycle mutated device queue_alloc; reflect back to the host copy
     plan.queue_alloc.copy_(q_alloc.cpu())
     return res
