@@ -45,6 +45,14 @@ PLUGIN_ARGS = """\
   session-open check is used.
   Also: `deviceshare.schedule-policy` (`binpack` | `spread`),
   `deviceshare.gpu-score-weight`.
+- `numaaware` — `exact` (default `false`): pin the CPU request of a Pod
+  with the annotation `volcano.sh/numa-topology-policy` (`single-numa-node`,
+  `restricted`, `best-effort`) to a NUMA zone inside the allocate cycle, per
+  placement, on the device.  Under the first two every bound Pod then
+  carries `volcano.sh/numa-node` (and `volcano.sh/cpuset`); a Pod no zone
+  holds stays pending.  Needs at most 8 zones per Node and CPU quantities
+  in whole millicores below 2^28; otherwise, and under the soft-shard
+  coordinator, the session-open check and the host choice are used.
 """
 
 

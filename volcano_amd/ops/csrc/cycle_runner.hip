@@ -20,6 +20,7 @@ namespace {
 const int CHAIN_MIN = 32;     // shortest run of jobs worth a chain
 const int BULK_TASKS = 512;   // classes this large take the bulk select
 const int MODE_HYPERNODE = 3; // class_mode of a network-topology class
+const int NUMA_HARD = 1;      // class_numa_req policy that clamps the cap
 
 // The opt-in paths, read once per cycle so tests can flip them.
 //
@@ -105,6 +106,8 @@ struct ClassView {
     int32_t* dom_count;          // [D]
     // device request (count, memory, cores); null = none
     const int32_t* dev;
+    // NUMA request (cpu millicores, policy); null = none
+    const int32_t* numa;
 };
 
 struct Runner {
@@ -112,6 +115,7 @@ struct Runner {
     hipStream_t stream;
     const bool domains_live;
     const bool devices_live;
+    const bool numa_live;
 
     Runner(const VamdCycle& c, hipStream_t s)
         : cy(c), stream(s),
@@ -122,7 +126,9 @@ struct Runner {
                        c.card_state != nullptr &&
                        c.card_mem_total != nullptr &&
                        c.class_dev_req != nullptr &&
-                       c.dev_assign != nullptr && c.card_K >= 1) {}
+                       c.dev_assign != nullptr && c.card_K >= 1),
+          numa_live(c.zone_free != nullptr && c.class_numa_req != nullptr &&
+                    c.numa_assign != nullptr && c.zone_Z >= 1) {}
 
     int group_of(int c) const { return domains_live ? cy.class_group[c] : -1; }
 
@@ -131,6 +137,18 @@ struct Runner {
         if (!devices_live) return nullptr;
         const int32_t* rq = cy.class_dev_req + (size_t)c * 4;
         return rq[0] > 0 ? rq : nullptr;
+    }
+
+    // the class's NUMA request row, or null
+    const int32_t* numa_of(int c) const {
+        if (!numa_live) return nullptr;
+        const int32_t* rq = cy.class_numa_req + (size_t)c * 2;
+        return rq[1] != 0 ? rq : nullptr;
+    }
+
+    // packed per card or per zone: the split path only
+    bool packed(int c) const {
+        return dev_of(c) != nullptr || numa_of(c) != nullptr;
     }
 
     ClassView view(int j, int c) const {
@@ -148,7 +166,7 @@ struct Runner {
             cy.log_nodes + cd.log_off, cy.log_counts + cd.log_off,
             cy.log_len + c, cy.class_placed + c, cy.job_placed + j,
             cy.job_flag + j, single ? gang_fuse_min(job, cd) : -1,
-            g, 0, 0, 0, nullptr, nullptr, dev_of(c)};
+            g, 0, 0, 0, nullptr, nullptr, dev_of(c), numa_of(c)};
         if (g >= 0) {
             v.mode = cy.class_mode != nullptr ? cy.class_mode[c] : 0;
             if (v.mode == 0) v.skew = cy.class_skew[c];
@@ -222,7 +240,24 @@ struct Runner {
                            v.cd.log_cap, stream);
     }
 
+    void numa_cap(const ClassView& v) const {
+        vamd_numa_cap(cy.score_scratch, cy.cap_scratch, cy.zone_free,
+                      v.numa[0], cy.zone_Z, cy.N, stream);
+    }
+
+    void numa_commit(const ClassView& v) const {
+        vamd_numa_commit(v.log_nodes, v.log_counts, v.log_len, cy.zone_free,
+                         cy.numa_assign + (size_t)v.cd.log_off * cy.zone_Z,
+                         v.numa[0], cy.zone_Z, cy.N, v.cd.log_cap, stream);
+    }
+
     void revert(const ClassView& v) const {
+        // the zone plane gives back what the assignment rows recorded
+        if (v.numa != nullptr)
+            vamd_numa_revert(
+                v.job_flag, v.log_nodes, v.log_len, cy.zone_free,
+                cy.numa_assign + (size_t)v.cd.log_off * cy.zone_Z, v.numa[0],
+                cy.zone_Z, cy.N, v.cd.log_cap, stream);
         // the card planes give back what the assignment rows recorded
         if (v.dev != nullptr)
             vamd_device_revert(
@@ -243,12 +278,15 @@ struct Runner {
                          v.job_placed, cy.N, cy.R, stream);
     }
 
-    // A class with a device request: always the split path, the per-card
-    // clamp right after the score so that every domain rule reads the
-    // clamped cap, the slices taken after the select (and count update).
-    void run_device_class(const ClassView& v) const {
+    // A class with a device or NUMA request: always the split path, the
+    // per-card and per-zone clamps right after the score so that every
+    // domain rule reads the clamped cap, the slices and zones taken after
+    // the select (and count update).  Only a hard NUMA policy clamps; a
+    // best-effort class pins what fits and leaves the rest unpinned.
+    void run_packed_class(const ClassView& v) const {
         score(v);
-        device_cap(v);
+        if (v.dev != nullptr) device_cap(v);
+        if (v.numa != nullptr && v.numa[1] == NUMA_HARD) numa_cap(v);
         if (v.group >= 0 && v.mode == 0) {
             spread_select(v);
         } else {
@@ -257,12 +295,13 @@ struct Runner {
             if (v.group >= 0 && v.mode != MODE_HYPERNODE)
                 domain_count_add(v);
         }
-        device_commit(v);
+        if (v.dev != nullptr) device_commit(v);
+        if (v.numa != nullptr) numa_commit(v);
     }
 
     void run_class(const ClassView& v) const {
-        if (v.dev != nullptr) {
-            run_device_class(v);
+        if (v.dev != nullptr || v.numa != nullptr) {
+            run_packed_class(v);
         } else if (v.group >= 0 && v.mode == MODE_HYPERNODE) {
             // network topology: the mask confines the class to the one
             // hypernode chosen from the live cap; the group's slice is a
@@ -312,13 +351,13 @@ struct Runner {
             revert(view(j, c));
     }
 
-    // a single-class small job without a domain rule or device request;
+    // a single-class small job without a domain rule, device or NUMA request;
     // anything else breaks a chain run
     bool chainable(int j) const {
         const VamdJobDesc& jb = cy.jobs[j];
         return jb.class_end - jb.class_begin == 1 &&
             group_of(jb.class_begin) < 0 &&
-            dev_of(jb.class_begin) == nullptr &&
+            !packed(jb.class_begin) &&
             cy.classes[jb.class_begin].ntasks < BULK_TASKS;
     }
 
@@ -333,14 +372,14 @@ struct Runner {
         return e;
     }
 
-    // The megacycle kernel has no bulk, no domain-rule select and no card
-    // planes: such a plan runs per class.  False as well when the staging allocation
-    // fails: fall through to per-class launches.
+    // The megacycle kernel has no bulk, no domain-rule select and no card or
+    // zone planes: such a plan runs per class.  False as well when the
+    // staging allocation fails: fall through to per-class launches.
     bool try_megacycle() const {
         if (cy.n_classes < 32) return false;
         for (int c = 0; c < cy.n_classes; ++c)
             if (cy.classes[c].ntasks >= BULK_TASKS || group_of(c) >= 0 ||
-                    dev_of(c) != nullptr)
+                    packed(c))
                 return false;
         void* blob;
         VamdDevDescs dd;

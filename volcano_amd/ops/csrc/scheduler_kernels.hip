@@ -1548,6 +1548,152 @@ __global__ void __launch_bounds__(DS_THREADS) device_revert_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Numaaware: pinning CPU requests to NUMA zones, per placement.
+//
+// Oracle: NumaState.best_zone + take called once per pod
+// (scheduler/plugins/numaaware.py) — each pod takes its `cpu` millicores
+// from the zone with the SMALLEST free value that still fits (strictly
+// smaller wins, ties to the lower zone index).  On integer millicores two
+// facts make that closed-form, so nothing is simulated here:
+//   * capacity: zones are independent, zone z has free_z / cpu slots, and a
+//     node pins exactly S = sum of slots pods of the shape;
+//   * fill order: the chosen zone only gets smaller, so it stays the strict
+//     minimum among fitting zones until it has no slot left, and the other
+//     zones do not move; m pods in a row fill the zones in the order
+//     (free asc, index asc) among zones with slots, each to its slot count.
+// zone_free is int32 [Z, N] (Z <= 8 zones, zone-major like the resource and
+// card planes: a wave reads 64 consecutive nodes of one zone), 0 for the
+// missing zones of a smaller node.  0 <= free < 2^28 and cpu >= 1
+// (host-checked), so free << 3 | zone is a 31-bit sort key, take * cpu
+// never exceeds free, and S <= 8 * (2^28 - 1) is summed in int64.
+// ---------------------------------------------------------------------------
+#define NUMA_MAX_ZONES 8
+#define NUMA_TAKE_BITS 28
+#define NUMA_TAKE_MASK ((1u << NUMA_TAKE_BITS) - 1u)
+#define NUMA_THREADS 256
+#define NUMA_ENTRIES_PER_WAVE (WAVE / NUMA_MAX_ZONES)
+
+DEVINL int zone_slots(int free, int cpu) { return free > 0 ? free / cpu : 0; }
+
+// Hard policies, after score_cap (and device_cap), before any domain rule:
+// cap = min(cap, S), and score = -inf where that leaves nothing
+// (score > -inf <=> cap > 0 holds).  Grid-stride, one thread per node; a
+// node with cap == 0 loads nothing.  The zone loop is unrolled over the
+// compile-time bound ZB, so no zone is ever indexed dynamically in
+// registers; its loads are independent and issue back to back.
+template <int ZB>
+__global__ void numa_cap_kernel(
+    float* __restrict__ score, int* __restrict__ cap,
+    const int* __restrict__ zone_free, int cpu, int Z, int N)
+{
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N;
+         i += gridDim.x * blockDim.x) {
+        const int c = cap[i];
+        if (c <= 0) continue;
+        int free[ZB];
+#pragma unroll
+        for (int z = 0; z < ZB; ++z)
+            free[z] = z < Z ? zone_free[(size_t)z * N + i] : 0;
+        long long S = 0;
+#pragma unroll
+        for (int z = 0; z < ZB; ++z)
+            S += zone_slots(free[z], cpu);
+        if (S < (long long)c) {
+            cap[i] = (int)S;
+            if (S == 0) score[i] = NEG_INF;
+        }
+    }
+}
+
+// After the select (and count update, and device_commit): the logged
+// placements take their zones.  One 8-lane group per log entry (node, cnt),
+// eight entries per wave, grid-stride over *log_len; lane z holds zone z of
+// the entry's node.  A zone with slots carries the sort key free << 3 | z,
+// one without a key above all of those (bit 31 | z), so ONE unsigned
+// compare per peer gives both the fill order and the place of the unused
+// zones behind it: rank = keys below mine, prefix = their slots, both from
+// width-8 shuffles; take = clamp(cnt - prefix, 0, slots).  A hard class
+// never logs more than S (numa_cap clamped it); a best-effort class may, and
+// the surplus pods simply find no zone.  Each lane subtracts take * cpu from
+// its own zone with a plain store and writes ONE word of the entry's
+// assignment row at position `rank`: zone << 28 | take (0 without a take,
+// which fills the tail).  A class logs a node at most once: entries never
+// share a zone, so there are no atomics.  The loop bound is the same for
+// every lane of a wave — all 64 lanes stay active through the shuffles.
+__global__ void __launch_bounds__(NUMA_THREADS) numa_commit_kernel(
+    const int* __restrict__ log_nodes, const int* __restrict__ log_counts,
+    const int* __restrict__ log_len, int* __restrict__ zone_free,
+    int* __restrict__ assign,             // [L, Z]
+    int cpu, int Z, int N, int L)
+{
+    int len = *log_len;
+    if (len > L) len = L;
+    const int z = threadIdx.x & (NUMA_MAX_ZONES - 1);
+    const int group = (blockIdx.x * blockDim.x + threadIdx.x) / NUMA_MAX_ZONES;
+    const int sub = group & (NUMA_ENTRIES_PER_WAVE - 1);
+    const int groups = gridDim.x * blockDim.x / NUMA_MAX_ZONES;
+    for (int base = group - sub; base < len; base += groups) {
+        const int e = base + sub;
+        const bool row = e < len && z < Z;
+        int node = -1, cnt = 0;
+        if (row) { node = log_nodes[e]; cnt = log_counts[e]; }
+        const bool live = row && cnt > 0 && node >= 0 && node < N;
+        const size_t o = live ? (size_t)z * N + node : 0;
+        const int free = live ? zone_free[o] : 0;
+        const int slots = zone_slots(free, cpu);
+        const unsigned key = slots > 0
+            ? ((unsigned)free << 3) | (unsigned)z : 0x80000000u | (unsigned)z;
+        int rank = 0;
+        long long prefix = 0;
+#pragma unroll
+        for (int j = 0; j < NUMA_MAX_ZONES; ++j) {
+            const unsigned key_j = (unsigned)__shfl((int)key, j, NUMA_MAX_ZONES);
+            const int s_j = __shfl(slots, j, NUMA_MAX_ZONES);
+            const bool first = key_j < key;
+            rank += first;
+            prefix += first ? s_j : 0;
+        }
+        long long t = (long long)cnt - prefix;
+        if (t > slots) t = slots;
+        const int take = t > 0 ? (int)t : 0;
+        if (take > 0) zone_free[o] = free - take * cpu;
+        // lanes z >= Z rank behind every real zone: rank < Z exactly for row
+        if (row)
+            assign[(size_t)e * Z + rank] = take > 0
+                ? (int)(((unsigned)z << NUMA_TAKE_BITS) | (unsigned)take) : 0;
+    }
+}
+
+// Multi-class gang revert (beside cond_revert / spread_revert /
+// device_revert), gated on the job flag: gives back exactly what the
+// assignment rows recorded and zeroes them.  Same 8-lane groups; lane p
+// owns position p of the row, and the positions of a row name distinct
+// zones.
+__global__ void __launch_bounds__(NUMA_THREADS) numa_revert_kernel(
+    const uint8_t* __restrict__ flag, const int* __restrict__ log_nodes,
+    const int* __restrict__ log_len, int* __restrict__ zone_free,
+    int* __restrict__ assign, int cpu, int Z, int N, int L)
+{
+    if (*flag) return;
+    int len = *log_len;
+    if (len > L) len = L;
+    const int p = threadIdx.x & (NUMA_MAX_ZONES - 1);
+    if (p >= Z) return;
+    const int groups = gridDim.x * blockDim.x / NUMA_MAX_ZONES;
+    for (int e = (blockIdx.x * blockDim.x + threadIdx.x) / NUMA_MAX_ZONES;
+         e < len; e += groups) {
+        const unsigned v = (unsigned)assign[(size_t)e * Z + p];
+        if (v == 0) continue;
+        assign[(size_t)e * Z + p] = 0;
+        const int zone = (int)(v >> NUMA_TAKE_BITS);
+        const int take = (int)(v & NUMA_TAKE_MASK);
+        const int node = log_nodes[e];
+        if (zone >= Z || node < 0 || node >= N) continue;
+        zone_free[(size_t)zone * N + node] += take * cpu;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Megacycle: a WHOLE small-class plan in ONE launch.  Heterogeneous
 // inventories produce thousands of per-job classes; at ~2 enqueues per
 // class the cycle becomes launch-bound.  This kernel sequences the
@@ -2174,6 +2320,60 @@ void vamd_device_revert(
                        dim3(DS_THREADS), 0, stream, flag, log_nodes, log_len,
                        card_mem_used, card_cores_used, card_state, assign,
                        memory, cores, K, N, L);
+}
+
+int vamd_numa_max_zones(void) { return NUMA_MAX_ZONES; }
+
+// a request the kernels cannot divide by or index with launches nothing
+static bool numa_shape_ok(int cpu, int Z)
+{
+    return cpu >= 1 && Z >= 1 && Z <= NUMA_MAX_ZONES;
+}
+
+static int numa_log_blocks(int L)
+{
+    const int per_block = NUMA_THREADS / NUMA_MAX_ZONES;
+    int blocks = min((L + per_block - 1) / per_block, 256);
+    return blocks < 1 ? 1 : blocks;
+}
+
+void vamd_numa_cap(float* score, int* cap, const int* zone_free, int cpu,
+                   int Z, int N, hipStream_t stream)
+{
+    if (!numa_shape_ok(cpu, Z)) return;
+    int threads = 256;
+    int blocks = min((N + threads - 1) / threads, 4096);
+    if (blocks < 1) blocks = 1;
+#define VAMD_NUMA_CAP(ZB)                                                    \
+    hipLaunchKernelGGL(vamd::numa_cap_kernel<ZB>, dim3(blocks),              \
+                       dim3(threads), 0, stream, score, cap, zone_free, cpu, \
+                       Z, N)
+    if (Z <= 2) VAMD_NUMA_CAP(2);
+    else if (Z <= 4) VAMD_NUMA_CAP(4);
+    else VAMD_NUMA_CAP(8);
+#undef VAMD_NUMA_CAP
+}
+
+void vamd_numa_commit(
+    const int* log_nodes, const int* log_counts, const int* log_len,
+    int* zone_free, int* assign, int cpu, int Z, int N, int L,
+    hipStream_t stream)
+{
+    if (!numa_shape_ok(cpu, Z)) return;
+    hipLaunchKernelGGL(vamd::numa_commit_kernel, dim3(numa_log_blocks(L)),
+                       dim3(NUMA_THREADS), 0, stream, log_nodes, log_counts,
+                       log_len, zone_free, assign, cpu, Z, N, L);
+}
+
+void vamd_numa_revert(
+    const uint8_t* flag, const int* log_nodes, const int* log_len,
+    int* zone_free, int* assign, int cpu, int Z, int N, int L,
+    hipStream_t stream)
+{
+    if (!numa_shape_ok(cpu, Z)) return;
+    hipLaunchKernelGGL(vamd::numa_revert_kernel, dim3(numa_log_blocks(L)),
+                       dim3(NUMA_THREADS), 0, stream, flag, log_nodes, log_len,
+                       zone_free, assign, cpu, Z, N, L);
 }
 
 void vamd_batch_score(const VamdCycle& cy, const VamdDevDescs& dd, int c0,

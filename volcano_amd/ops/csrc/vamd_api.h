@@ -149,6 +149,44 @@ __attribute__((weak)) void vamd_device_revert(
 // Largest K of the card planes.
 __attribute__((weak)) int vamd_device_max_cards(void);
 
+// --- numaaware: pinning CPU requests to NUMA zones -------------------------
+//
+// zone_free is an int32 plane [Z, N] (zone-major), Z <= vamd_numa_max_zones():
+// free millicores of zone z of node n, 0 <= free < 2^28, 0 for the missing
+// zones of a smaller node.  A request is `cpu` >= 1 millicores that must
+// come from ONE zone.  The rule is NumaState.best_zone / take once per pod
+// (the smallest zone that still fits, ties to the lower index), computed in
+// closed form: zone z has free / cpu slots, zones fill in the order
+// (free asc, index asc) among zones with slots.
+//
+// The three launchers are weak, like the device-share ones.
+
+// Hard policies only, after vamd_score_cap (and vamd_device_cap), before any
+// domain rule: cap = min(cap, S) with S the node's slots; score = -inf
+// where that is 0.
+__attribute__((weak)) void vamd_numa_cap(
+    float* score, int* cap, const int* zone_free, int cpu, int Z, int N,
+    hipStream_t stream);
+
+// After the select: the first min(log_counts[e], S) pods of entry
+// e < *log_len (<= L) take a zone each on node log_nodes[e]; the rest stay
+// unpinned.  assign[L, Z]: the used zones of entry e in fill order,
+// zone << 28 | take; the tail is 0.
+__attribute__((weak)) void vamd_numa_commit(
+    const int* log_nodes, const int* log_counts, const int* log_len,
+    int* zone_free, int* assign, int cpu, int Z, int N, int L,
+    hipStream_t stream);
+
+// When *flag == 0: gives back what the assignment rows recorded and zeroes
+// them (beside vamd_cond_revert / vamd_spread_revert / vamd_device_revert).
+__attribute__((weak)) void vamd_numa_revert(
+    const uint8_t* flag, const int* log_nodes, const int* log_len,
+    int* zone_free, int* assign, int cpu, int Z, int N, int L,
+    hipStream_t stream);
+
+// Largest Z of the zone plane.
+__attribute__((weak)) int vamd_numa_max_zones(void);
+
 // --- whole-cycle runner ----------------------------------------------------
 
 // One task class (a batch of identical pending tasks of one job).
@@ -262,6 +300,13 @@ struct VamdCycle {
     int32_t* dev_assign;           // [L, card_K], parallel to the log
     int32_t card_K;
     int32_t _pad2;
+    // NUMA block: live only when all of it is set (zone_Z >= 1)
+    int32_t* zone_free;            // [zone_Z, N]
+    const int32_t* class_numa_req; // HOST [C, 2]: cpu millicores, policy
+                                   //   (0 = none, 1 = hard, 2 = best-effort)
+    int32_t* numa_assign;          // [L, zone_Z], parallel to the log
+    int32_t zone_Z;
+    int32_t _pad3;
 };
 
 // Device copies of the descriptor arrays (chain and megacycle paths).
@@ -318,6 +363,13 @@ void vamd_megacycle(const VamdCycle& cy, const VamdDevDescs& dd,
 //     fused, chain or megacycle path — and its multi-class revert runs
 //     vamd_device_revert beside the existing one.  With the block dead
 //     nothing changes a single launch.
+//   * A class with a NUMA request (NUMA block live, class_numa_req[c]
+//     .policy != 0) takes the same split path: vamd_score_cap ->
+//     [vamd_device_cap] -> [vamd_numa_cap, hard policy only] -> [its domain
+//     rule] -> select (bulk by size) -> [count update] ->
+//     [vamd_device_commit] -> vamd_numa_commit, and its multi-class revert
+//     runs vamd_numa_revert as well.  With the block dead nothing changes a
+//     single launch.
 // Returns 0; nonzero, before any HIP call, when cy->struct_size is not
 // sizeof(VamdCycle).
 int vamd_run_cycle(const VamdCycle* cy, hipStream_t stream);

@@ -16,8 +16,8 @@ from typing import Optional
 import torch
 
 from .build import LIB_PATH, build
-from .reference import (DEV_MAX_CARDS, check_device_request,
-                        check_hypernode_table)
+from .reference import (DEV_MAX_CARDS, NUMA_MAX_ZONES, check_device_request,
+                        check_hypernode_table, check_numa_request)
 
 _lib = None
 
@@ -61,7 +61,10 @@ class VamdCycle(Structure):
         "count_off", "domains", "domain_scratch", "group_row",
         "card_mem_used", "card_cores_used", "card_state", "card_mem_total",
         "class_dev_req", "dev_assign")] + [
-        ("card_K", c_int32), ("_pad2", c_int32)]
+        ("card_K", c_int32), ("_pad2", c_int32)] + [
+        (n, c_void_p) for n in (
+            "zone_free", "class_numa_req", "numa_assign")] + [
+        ("zone_Z", c_int32), ("_pad3", c_int32)]
 
 
 def _load():
@@ -102,6 +105,14 @@ def _load():
         raise RuntimeError(
             "the loaded kernel library and this module disagree on "
             "DEV_MAX_CARDS; rebuild (python -m volcano_amd.ops.build)")
+    lib.vamd_numa_cap.restype = None
+    lib.vamd_numa_commit.restype = None
+    lib.vamd_numa_revert.restype = None
+    lib.vamd_numa_max_zones.restype = c_int
+    if lib.vamd_numa_max_zones() != NUMA_MAX_ZONES:
+        raise RuntimeError(
+            "the loaded kernel library and this module disagree on "
+            "NUMA_MAX_ZONES; rebuild (python -m volcano_amd.ops.build)")
     _lib = lib
     return lib
 
@@ -369,6 +380,67 @@ def device_revert(flag, log_nodes, log_len, mem_used, cores_used, state,
         c_int(N), c_int(L), _stream())
 
 
+def _zone_plane(op, zone_free):
+    """(Z, N) of a zone plane, checked."""
+    if zone_free.dim() != 2 or not 1 <= zone_free.shape[0] <= NUMA_MAX_ZONES \
+            or zone_free.dtype != torch.int32 \
+            or not zone_free.is_contiguous():
+        raise ValueError(f"{op}: zone_free is contiguous int32 [Z, N], "
+                         f"1 <= Z <= {NUMA_MAX_ZONES}")
+    return zone_free.shape
+
+
+def _zone_rows(op, assign, L, Z):
+    if assign.shape != (L, Z) or assign.dtype != torch.int32 \
+            or not assign.is_contiguous():
+        raise ValueError(f"{op}: assign is contiguous int32 [L, Z], "
+                         "parallel to the log")
+
+
+def numa_cap(score, cap, zone_free, cpu):
+    """Per-zone clamp of a hard NUMA policy (after score_cap and
+    device_cap, before any domain rule): ``cap = min(cap, S)`` with ``S``
+    the pods of ``cpu`` millicores the node's zones [Z, N] still pin;
+    ``score = -inf`` where that leaves 0.  Both change in place."""
+    lib = _load()
+    cpu, _ = check_numa_request(cpu, 1)
+    Z, N = _zone_plane("numa_cap", zone_free)
+    if score.shape != (N,) or cap.shape != (N,):
+        raise ValueError("numa_cap: score and cap need one entry per node")
+    lib.vamd_numa_cap(_p(score), _p(cap), _p(zone_free), c_int(cpu), c_int(Z),
+                      c_int(N), _stream())
+
+
+def numa_commit(log_nodes, log_counts, log_len, zone_free, assign, cpu):
+    """The logged placements take their zones (after the select); pods
+    past what the zones pin stay unpinned.  ``assign`` [L, Z] int32
+    receives, per log entry, the used zones in fill order as
+    ``zone << 28 | take``."""
+    lib = _load()
+    cpu, _ = check_numa_request(cpu, 1)
+    Z, N = _zone_plane("numa_commit", zone_free)
+    L = log_nodes.shape[0]
+    if log_counts.shape[0] != L:
+        raise ValueError("numa_commit: log_nodes and log_counts differ")
+    _zone_rows("numa_commit", assign, L, Z)
+    lib.vamd_numa_commit(
+        _p(log_nodes), _p(log_counts), _p(log_len), _p(zone_free), _p(assign),
+        c_int(cpu), c_int(Z), c_int(N), c_int(L), _stream())
+
+
+def numa_revert(flag, log_nodes, log_len, zone_free, assign, cpu):
+    """When ``flag`` is 0: the zones get back what ``assign`` recorded,
+    and ``assign`` is zeroed."""
+    lib = _load()
+    cpu, _ = check_numa_request(cpu, 1)
+    Z, N = _zone_plane("numa_revert", zone_free)
+    L = log_nodes.shape[0]
+    _zone_rows("numa_revert", assign, L, Z)
+    lib.vamd_numa_revert(
+        _p(flag), _p(log_nodes), _p(log_len), _p(zone_free), _p(assign),
+        c_int(cpu), c_int(Z), c_int(N), c_int(L), _stream())
+
+
 def fused_score_select(alloc_t, used_t, extra_t, ready, taints, planes_t,
                        req, tolerated, require, forbid, w_least, w_most,
                        w_bal, dim_w, bias, score, cap, ntasks,
@@ -408,7 +480,7 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
               class_forbid, class_min, dim_w, queue_alloc, queue_limit,
               score_scratch, cap_scratch, log_nodes, log_counts, log_len,
               class_placed, job_placed, job_flag, sort_scratch=None,
-              spread=None, devices=None):
+              spread=None, devices=None, numa=None):
     """One library call = one whole allocate cycle (plan built host-side).
 
     ``class_descs`` / ``job_descs`` are host buffers of ``VamdClassDesc`` /
@@ -431,7 +503,12 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
     card planes ``mem_used``/``cores_used``/``state`` device i32 [K, N],
     ``mem_total`` device i32 [N], ``class_req`` host int32 numpy [C, 4]
     (count, memory, cores, 0; count 0 = no request) and ``assign`` device
-    i32 [L, K] (zeroed), parallel to the log."""
+    i32 [L, K] (zeroed), parallel to the log.
+
+    ``numa`` (plans with NUMA-request classes only) is a dict:
+    ``zone_free`` device i32 [Z, N], ``class_req`` host int32 numpy [C, 2]
+    (cpu millicores, policy: 0 = none, 1 = hard, 2 = best-effort) and
+    ``assign`` device i32 [L, Z] (zeroed), parallel to the log."""
     lib = _load()
     R, N = alloc_t.shape
     cy = VamdCycle(
@@ -490,6 +567,20 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
         cy.class_dev_req = creq.ctypes.data
         cy.dev_assign = _addr(devices["assign"])
         cy.card_K = K
+    if numa is not None:
+        Z, zn = _zone_plane("run_cycle", numa["zone_free"])
+        nreq = numa["class_req"]
+        if zn != N or nreq.shape != (n_classes, 2) \
+                or nreq.dtype != "int32" or not nreq.flags["C_CONTIGUOUS"]:
+            raise ValueError("run_cycle: numa.zone_free must be [Z, N] and "
+                             "numa.class_req int32 [C, 2]")
+        for row in nreq[nreq[:, 1] != 0]:
+            check_numa_request(*row)
+        _zone_rows("run_cycle", numa["assign"], log_nodes.shape[0], Z)
+        cy.zone_free = _addr(numa["zone_free"])
+        cy.class_numa_req = nreq.ctypes.data
+        cy.numa_assign = _addr(numa["assign"])
+        cy.zone_Z = Z
     rc = lib.vamd_run_cycle(ctypes.byref(cy), _stream())
     if rc != 0:
         raise RuntimeError(

@@ -731,6 +731,137 @@ def device_cards(row, cnt: int, count: int):
     return [seq[i * count:(i + 1) * count] for i in range(cnt)]
 
 
+# -- numaaware: pinning CPU requests to NUMA zones --------------------------
+#
+# ``zone_free`` is a CPU int32 tensor [Z, N]: free millicores per zone, 0 for
+# the missing zones of a smaller node.  A request is ``cpu`` millicores that
+# must come from one zone.  The oracles are the plain per-pod loop of
+# ``NumaState.best_zone`` / ``take`` on integers (the host's +0.1 slack is
+# nothing there); ``numa_slots`` is the closed form the HIP kernels compute.
+
+NUMA_MAX_ZONES = 8              # Z of the zone plane
+NUMA_FREE_LIMIT = 1 << 28       # a zone's free millicores stay below this
+NUMA_TAKE_BITS = 28             # assignment word: zone << 28 | take
+NUMA_HARD, NUMA_BEST_EFFORT = 1, 2      # single-numa-node / restricted; soft
+
+
+def check_numa_request(cpu, policy):
+    """(cpu, policy) as ints, or ValueError."""
+    cpu, policy = int(cpu), int(policy)
+    if not 1 <= cpu < NUMA_FREE_LIMIT or \
+            policy not in (NUMA_HARD, NUMA_BEST_EFFORT):
+        raise ValueError(f"numa request {(cpu, policy)}: 1 <= cpu < 2^28, "
+                         "policy 1 (hard) or 2 (best-effort)")
+    return cpu, policy
+
+
+def _zone_plane(zone_free):
+    if zone_free.device.type != "cpu" or zone_free.dtype != torch.int32 \
+            or zone_free.dim() != 2:
+        raise ValueError("numa oracles take a CPU int32 zone plane [Z, N]")
+    return zone_free.numpy()
+
+
+def _best_zone(free, cpu: int):
+    """``NumaState.best_zone`` on integers: the smallest zone that fits,
+    the strict ``<`` leaving ties to the lower index."""
+    best = None
+    for z, f in enumerate(free):
+        if f >= cpu and (best is None or f < free[best]):
+            best = z
+    return best
+
+
+def numa_cap(score, cap, zone_free, cpu: int) -> None:
+    """``cap[n] = min(cap[n], pods best_zone pins in a row)``,
+    ``score[n] = -inf`` where that is 0 — the oracle of the HIP
+    ``numa_cap`` (hard policies only)."""
+    cpu, _ = check_numa_request(cpu, NUMA_HARD)
+    zf = _zone_plane(zone_free)
+    cap_h = cap.cpu()
+    for n in torch.nonzero(cap_h > 0).flatten().tolist():
+        free = zf[:, n].tolist()
+        fit = 0
+        while fit < int(cap_h[n]):
+            z = _best_zone(free, cpu)
+            if z is None:
+                break
+            free[z] -= cpu
+            fit += 1
+        if fit < int(cap_h[n]):
+            cap[n] = fit
+            if fit == 0:
+                score[n] = NEG_INF
+
+
+def numa_commit(log_nodes, log_counts, log_len, zone_free, assign,
+                cpu: int) -> None:
+    """Every logged pod asks ``best_zone`` and takes its request, one pod
+    at a time; a pod that finds no zone stays unpinned.  ``assign`` [L, Z]
+    (CPU int32) records, per entry, the run-length form of the picked
+    zones: ``zone << 28 | take`` in pick order, then zeros — the oracle of
+    the HIP ``numa_commit``."""
+    cpu, _ = check_numa_request(cpu, NUMA_HARD)
+    zf = _zone_plane(zone_free)
+    rows = assign.numpy().view("uint32")
+    nodes, counts = log_nodes.cpu().tolist(), log_counts.cpu().tolist()
+    for e in range(min(int(log_len), len(nodes))):
+        rows[e] = 0
+        n = nodes[e]
+        free = zf[:, n].tolist() if counts[e] > 0 else []
+        runs = []                           # [zone, take] in pick order
+        for _ in range(max(counts[e], 0)):
+            z = _best_zone(free, cpu)
+            if z is None:
+                break
+            free[z] -= cpu
+            if runs and runs[-1][0] == z:
+                runs[-1][1] += 1
+            else:
+                runs.append([z, 1])
+        for p, (z, take) in enumerate(runs):
+            rows[e, p] = (z << NUMA_TAKE_BITS) | take
+            zf[z, n] = free[z]
+
+
+def numa_revert(flag, log_nodes, log_len, zone_free, assign,
+                cpu: int) -> None:
+    """When ``flag`` is 0 the zones get back what ``assign`` recorded
+    (``NumaState.give`` per pod) and ``assign`` is zeroed."""
+    if int(flag) != 0:
+        return
+    cpu, _ = check_numa_request(cpu, NUMA_HARD)
+    zf = _zone_plane(zone_free)
+    rows = assign.numpy().view("uint32")
+    nodes = log_nodes.cpu().tolist()
+    for e in range(min(int(log_len), len(nodes))):
+        for word in rows[e].tolist():
+            for _ in range(word & ((1 << NUMA_TAKE_BITS) - 1)):
+                zf[word >> NUMA_TAKE_BITS, nodes[e]] += cpu
+        rows[e] = 0
+
+
+def numa_slots(zone_free, cpu: int):
+    """Closed form: slots per zone [Z, N] (int64 numpy) — how many pods of
+    ``cpu`` millicores each zone still pins; a node pins exactly
+    ``slots.sum(0)`` of them, and they fill the zones in the order
+    (free asc, index asc) among zones with slots, each to its count."""
+    import numpy as np
+    cpu, _ = check_numa_request(cpu, NUMA_HARD)
+    zf = _zone_plane(zone_free).astype(np.int64)
+    return np.where(zf > 0, zf // cpu, 0)
+
+
+def numa_zones(row, cnt: int):
+    """One zone (or None: unpinned) per pod from an assignment row: the
+    row spells the zone sequence, the pods past its end found no zone."""
+    seq = []
+    for word in (int(w) & 0xFFFFFFFF for w in row):
+        seq.extend([word >> NUMA_TAKE_BITS]
+                   * (word & ((1 << NUMA_TAKE_BITS) - 1)))
+    return (seq + [None] * cnt)[:cnt]
+
+
 def drf_share(job_alloc: torch.Tensor, total: torch.Tensor) -> torch.Tensor:
     """Dominant share per job: max_r alloc/total (drf.go calculateShare).
 

@@ -24,6 +24,7 @@ from typing import Dict, List
 import numpy as np
 
 from ...api.info import TaskClass
+from ...api.resource import CPU as _CPU
 from ...api.types import PodGroupPhase, TaskStatus
 
 PENDING_S = TaskStatus.PENDING
@@ -342,6 +343,39 @@ class AllocateAction:
                 if elig_l[ix] and device_job(jb):
                     elig_l[ix] = False
 
+        # exact NUMA pinning (numaaware plugin, ``exact: true``): a class
+        # with a topology policy is pinned per zone on the device, per
+        # placement.  Not under the soft-shard coordinator, which keeps the
+        # host bit and the host choice.
+        numa_exact = getattr(ssn, "numa_exact", None) \
+            if self.coordinator is None else None
+
+        def numa_attach(cp: ClassPlan) -> None:
+            """Attach cp's NUMA request, if it has one; its constraint words
+            lose the session-open ``numa-unfit:`` bit (copy first, the
+            memoized arrays are shared)."""
+            if numa_exact is None:
+                return
+            rq = numa_exact.request_of(cp.tclass.tasks[0])
+            if rq is None:
+                return
+            if plan.numa_state is None:
+                plan.set_numa_state(numa_exact.plane)
+            plan.add_numa_request(cp, *rq)
+            bit = numa_exact.unfit_bits.get(cp.tclass.request.get(_CPU))
+            if bit is not None and bit // 64 < len(cp.forbid):
+                cp.forbid = cp.forbid.copy()
+                cp.forbid[bit // 64] &= ~(np.int64(1) << np.int64(bit % 64))
+
+        # such jobs never join a fused signature run
+        if numa_exact is not None and elig_l is not None:
+            for ix, jb in enumerate(jobs_l):
+                t0_ = next(iter(jb.task_status_index.get(
+                    _TS.PENDING, {}).values()), None) if elig_l[ix] else None
+                if t0_ is not None and \
+                        numa_exact.request_of(t0_) is not None:
+                    elig_l[ix] = False
+
         if hypernode_exact is not None and elig_l is not None:
             # each such job needs its own domain: none joins a fused run
             for ix, jb in enumerate(jobs_l):
@@ -494,8 +528,10 @@ class AllocateAction:
                     and af is None else None
                 dv = device_exact.request_of(first) \
                     if device_exact is not None else None
+                nu = numa_exact.request_of(first) \
+                    if numa_exact is not None else None
                 if sp is None and af is None and hn is None \
-                        and dv is None and not bias_fns \
+                        and dv is None and nu is None and not bias_fns \
                         and open_bundle is not None \
                         and open_key == (qi, sig):
                     tasks = list(pend.values())
@@ -561,11 +597,13 @@ class AllocateAction:
                     hypernode_attach(cp, job, hn, gang_min)
                 if dv is not None:
                     device_attach(cp)
-                # biased, domain-rule and device classes never fuse
+                if nu is not None:
+                    numa_attach(cp)
+                # biased, domain-rule, device and NUMA classes never fuse
                 if cp.bias is not None or cp.spread is not None \
                         or cp.affinity is not None \
                         or cp.hypernode is not None \
-                        or cp.device is not None:
+                        or cp.device is not None or cp.numa is not None:
                     close_bundle()
                     plan.add_job(job, [cp])
                 else:
@@ -619,6 +657,7 @@ class AllocateAction:
                     if af is not None:
                         affinity_attach(cp, af)
                 device_attach(cp)
+                numa_attach(cp)
                 classes.append(cp)
             if skipped and classes and job.min_available > sum(
                     c.tclass.count for c in classes) + job.occupied_count:
@@ -638,7 +677,8 @@ class AllocateAction:
                           and classes[0].spread is None
                           and classes[0].affinity is None
                           and classes[0].hypernode is None
-                          and classes[0].device is None)
+                          and classes[0].device is None
+                          and classes[0].numa is None)
             if bundleable:
                 cp = classes[0]
                 gang_min = max(job.min_available, cp.min_needed)
@@ -674,6 +714,13 @@ class AllocateAction:
                 id(cp.tclass): result.class_cards(c)
                 for c, cp in enumerate(plan.classes)
                 if cp.device is not None}
+        if result is not None and numa_exact is not None:
+            # the zones the cycle chose, handed over the same way and by
+            # the same two invariants (a NUMA class never bundles either)
+            numa_exact.zones = {
+                id(cp.tclass): result.class_zones(c)
+                for c, cp in enumerate(plan.classes)
+                if cp.numa is not None}
         if result is not None:
             self._gate_subgroup_families(plan, result)
             self._apply(ssn, plan, result, bad_nodes=bad)

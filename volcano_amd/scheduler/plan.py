@@ -133,6 +133,12 @@ class ClassPlan:
     # slices taken by device_commit after the select.  Composes with every
     # domain rule; never combined with ``bundle``.
     device: Optional[Tuple[int, int, int]] = None
+    # NUMA request (cpu millicores, policy: ref.NUMA_HARD /
+    # ref.NUMA_BEST_EFFORT) pinned per zone on the device
+    # (CyclePlan.add_numa_request): numa_cap after the score (hard only),
+    # the zones taken by numa_commit after the select.  Composes with every
+    # domain rule and with ``device``; never combined with ``bundle``.
+    numa: Optional[Tuple[int, int]] = None
 
     @property
     def ntasks(self) -> int:
@@ -162,9 +168,10 @@ class CycleResult:
     cold consumers (subgroup gating, tests)."""
 
     def __init__(self, plan, log_nodes, log_counts, log_len, class_placed,
-                 job_placed, job_flag, dev_assign=None):
+                 job_placed, job_flag, dev_assign=None, numa_assign=None):
         self.plan = plan
         self.dev_assign = dev_assign       # [L, K] i32, or None
+        self.numa_assign = numa_assign     # [L, Z] i32, or None
         self.log_nodes = log_nodes
         self.log_counts = log_counts
         self.log_len = log_len
@@ -207,6 +214,20 @@ class CycleResult:
                                             cnt, cp.device[0]))
         return out
 
+    def class_zones(self, c: int) -> List[Optional[int]]:
+        """The NUMA zone of every placed task of NUMA class c (None: the
+        pod is bound unpinned — best-effort only), in log order."""
+        cp = self.plan.classes[c]
+        if cp.numa is None or self.numa_assign is None:
+            return []
+        _, lc = self.class_entries(c)
+        out: List[Optional[int]] = []
+        for e, cnt in enumerate(lc.tolist()):
+            if cnt > 0:
+                out.extend(ref.numa_zones(self.numa_assign[cp.log_off + e],
+                                          cnt))
+        return out
+
     @property
     def class_results(self) -> List[ClassResult]:
         if self._class_results is None:
@@ -245,6 +266,33 @@ class CyclePlan:
         # (tensors on the runner's side, left for inspection)
         self.device_state: Optional[DeviceState] = None
         self.device_planes = None
+        # zone plane [Z, N] i32 at cycle start, and the live plane of the
+        # last run (a tensor on the runner's side, left for inspection)
+        self.numa_state: Optional[np.ndarray] = None
+        self.numa_plane = None
+
+    def set_numa_state(self, zone_free) -> None:
+        """The inventory's free millicores per NUMA zone ([Z, N] int32,
+        0 for the missing zones of a smaller node)."""
+        zone_free = np.ascontiguousarray(zone_free, dtype=np.int32)
+        if zone_free.ndim != 2 or zone_free.shape[1] != self.nt.n or \
+                not 1 <= zone_free.shape[0] <= ref.NUMA_MAX_ZONES:
+            raise ValueError("numa state: zone_free is [Z, N] with "
+                             f"1 <= Z <= {ref.NUMA_MAX_ZONES}")
+        if zone_free.max(initial=0) >= ref.NUMA_FREE_LIMIT or \
+                zone_free.min(initial=0) < 0:
+            raise ValueError("numa state: zone_free outside [0, 2^28)")
+        self.numa_state = zone_free
+
+    def add_numa_request(self, cp: ClassPlan, cpu: int, policy: int) -> None:
+        """Pin cp's instances per NUMA zone: ``cpu`` millicores each from
+        one zone; ``policy`` ref.NUMA_HARD clamps the capacity,
+        ref.NUMA_BEST_EFFORT pins what fits."""
+        if self.numa_state is None:
+            raise ValueError("numa request without numa state")
+        if cp.bundle is not None:
+            raise ValueError("numa classes never bundle")
+        cp.numa = ref.check_numa_request(cpu, policy)
 
     def set_device_state(self, mem_used, cores_used, state,
                          mem_total) -> None:
@@ -401,6 +449,10 @@ class CyclePlan:
                                           self.device_state is None):
                 raise ValueError(f"class {c}: a device class needs device "
                                  "state and never bundles")
+            if cp.numa is not None and (cp.bundle is not None or
+                                        self.numa_state is None):
+                raise ValueError(f"class {c}: a numa class needs numa "
+                                 "state and never bundles")
             for rule in (cp.spread, cp.affinity):
                 if rule is not None and self.spread_groups[rule[0]].row >= 0:
                     raise ValueError(f"class {c}: group {rule[0]} is a "
@@ -459,8 +511,19 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
                                  dtype=torch.int32)
         plan.device_planes = dict(zip(
             ("mem_used", "cores_used", "state", "mem_total"), cards))
+    # so do the zone plane and its rows: the oracle is the per-pod
+    # best_zone loop
+    zones = numa_assign = None
+    if any(cp.numa is not None for cp in plan.classes):
+        zones = torch.from_numpy(plan.numa_state.copy())
+        numa_assign = torch.zeros((plan.log_total, zones.shape[0]),
+                                  dtype=torch.int32)
+        plan.numa_plane = zones
 
     def revert(c, cp, flag, req, sl):
+        if cp.numa is not None:
+            ref.numa_revert(flag, log_nodes[sl], log_len[c], zones,
+                            numa_assign[sl], cp.numa[0])
         if cp.device is not None:
             ref.device_revert(flag, log_nodes[sl], log_len[c], *cards,
                               dev_assign[sl], cp.device)
@@ -494,6 +557,8 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
                           score, cap)
             if cp.device is not None:
                 ref.device_cap(score, cap, *cards, cp.device)
+            if cp.numa is not None and cp.numa[1] == ref.NUMA_HARD:
+                ref.numa_cap(score, cap, zones, cp.numa[0])
             sl = slice(cp.log_off, cp.log_off + cp.log_cap)
             if single:
                 # a discarded single-class gang leaves no trace (the HIP
@@ -547,6 +612,9 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
             if cp.device is not None:
                 ref.device_commit(log_nodes[sl], log_counts[sl], log_len[c],
                                   *cards, dev_assign[sl], cp.device)
+            if cp.numa is not None:
+                ref.numa_commit(log_nodes[sl], log_counts[sl], log_len[c],
+                                zones, numa_assign[sl], cp.numa[0])
         if not single:
             ref.finalize_job(job_placed[j], jp.occupied, jp.min_available,
                              class_placed[jp.class_begin:jp.class_end],
@@ -562,7 +630,8 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
                       log_counts.cpu().numpy(), log_len.cpu().numpy(),
                       class_placed.cpu().numpy(), job_placed.cpu().numpy(),
                       job_flag.cpu().numpy(),
-                      None if dev_assign is None else dev_assign.numpy())
+                      None if dev_assign is None else dev_assign.numpy(),
+                      None if numa_assign is None else numa_assign.numpy())
 
 
 def run_plan_hip(plan: CyclePlan) -> CycleResult:
@@ -729,6 +798,21 @@ def run_plan_hip(plan: CyclePlan) -> CycleResult:
         plan.device_planes = {k: devices[k] for k in (
             "mem_used", "cores_used", "state", "mem_total")}
 
+    # NUMA-request classes, the same way: one plane up, one request column
+    # host-side, one set of rows back
+    numa = None
+    if any(cp.numa is not None for cp in plan.classes):
+        nreq = np.zeros((C, 2), dtype=np.int32)
+        for c, cp in enumerate(plan.classes):
+            if cp.numa is not None:
+                nreq[c] = cp.numa
+        numa = dict(
+            zone_free=torch.from_numpy(plan.numa_state).to(dev),
+            class_req=nreq,
+            assign=torch.zeros((plan.log_total, plan.numa_state.shape[0]),
+                               dtype=torch.int32, device=dev))
+        plan.numa_plane = numa["zone_free"]
+
     hip.run_cycle(
         ctypes.c_void_p(cds.ctypes.data), C,
         ctypes.c_void_p(jds.ctypes.data), len(plan.jobs),
@@ -736,14 +820,16 @@ def run_plan_hip(plan: CyclePlan) -> CycleResult:
         nt.planes_t, bias, bias_rows, class_req, class_tol, class_require,
         class_forbid, class_min, dim_w, q_alloc, q_limit, score, cap,
         log_nodes, log_counts, log_len, class_placed, job_placed, job_flag,
-        sort_scratch, spread=spread, devices=devices)
+        sort_scratch, spread=spread, devices=devices, numa=numa)
 
     res = CycleResult(plan, log_nodes.cpu().numpy(),
                       log_counts.cpu().numpy(), log_len.cpu().numpy(),
                       class_placed.cpu().numpy(), job_placed.cpu().numpy(),
                       job_flag.cpu().numpy(),
                       None if devices is None
-                      else devices["assign"].cpu().numpy())
+                      else devices["assign"].cpu().numpy(),
+                      None if numa is None
+                      else numa["assign"].cpu().numpy())
     # the cycle mutated device queue_alloc; reflect back to the host copy
     plan.queue_alloc.copy_(q_alloc.cpu())
     return res
