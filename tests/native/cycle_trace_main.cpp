@@ -72,7 +72,10 @@ const char* const CANON[][2] = {
     {"dom_of", "dom_of"}, {"dom_count", "count"}, {"jobs_dev", "blob"},
     {"class_tol_dev", "blob"}, {"score_buf", "blob"}, {"topk_vals", "blob"},
     {"topk_ids", "blob"}, {"touched", "blob"}, {"touched_list", "blob"},
-    {"ptr", "blob"}, {"dst", "blob"}};
+    {"ptr", "blob"}, {"dst", "blob"},
+    {"card_mem_used", "*card_mem_used"},
+    {"card_cores_used", "*card_cores_used"}, {"card_state", "*card_state"},
+    {"card_mem_total", "*card_mem_total"}, {"zone_free", "*zone_free"}};
 
 std::vector<std::string> g_trace;   // calls of the plan being run
 int g_N, g_R, g_W;                  // its sizes
@@ -370,6 +373,76 @@ void vamd_megacycle(const VamdCycle& cy, const VamdDevDescs& dd,
         .p("job_flag", cy.job_flag).dims(cy.N, cy.R, cy.W);
 }
 
+// the six packing launchers are weak in vamd_api.h: defined here, the runner
+// of a plan with a device-share or NUMA block reaches these
+void vamd_device_cap(
+    float* score, int* cap, const int* card_mem_used,
+    const int* card_cores_used, const int* card_state,
+    const int* card_mem_total, int count, int memory, int cores, int K,
+    int N, hipStream_t stream)
+{
+    Line("device_cap", stream).p("score", score).p("cap", cap)
+        .p("card_mem_used", card_mem_used)
+        .p("card_cores_used", card_cores_used).p("card_state", card_state)
+        .p("card_mem_total", card_mem_total).i("count", count)
+        .i("memory", memory).i("cores", cores).i("K", K).dims(N, g_R, -1);
+}
+
+void vamd_device_commit(
+    const int* log_nodes, const int* log_counts, const int* log_len,
+    int* card_mem_used, int* card_cores_used, int* card_state,
+    const int* card_mem_total, int* assign, int count, int memory, int cores,
+    int K, int N, int L, hipStream_t stream)
+{
+    Line("device_commit", stream).p("log_nodes", log_nodes)
+        .p("log_counts", log_counts).p("log_len", log_len)
+        .p("card_mem_used", card_mem_used)
+        .p("card_cores_used", card_cores_used).p("card_state", card_state)
+        .p("card_mem_total", card_mem_total).p("assign", assign)
+        .i("count", count).i("memory", memory).i("cores", cores).i("K", K)
+        .dims(N, g_R, -1).i("L", L);
+}
+
+void vamd_device_revert(
+    const uint8_t* flag, const int* log_nodes, const int* log_len,
+    int* card_mem_used, int* card_cores_used, int* card_state, int* assign,
+    int memory, int cores, int K, int N, int L, hipStream_t stream)
+{
+    Line("device_revert", stream).p("flag", flag).p("log_nodes", log_nodes)
+        .p("log_len", log_len).p("card_mem_used", card_mem_used)
+        .p("card_cores_used", card_cores_used).p("card_state", card_state)
+        .p("assign", assign).i("memory", memory).i("cores", cores).i("K", K)
+        .dims(N, g_R, -1).i("L", L);
+}
+
+void vamd_numa_cap(float* score, int* cap, const int* zone_free, int cpu,
+                   int Z, int N, hipStream_t stream)
+{
+    Line("numa_cap", stream).p("score", score).p("cap", cap)
+        .p("zone_free", zone_free).i("cpu", cpu).i("Z", Z).dims(N, g_R, -1);
+}
+
+void vamd_numa_commit(
+    const int* log_nodes, const int* log_counts, const int* log_len,
+    int* zone_free, int* assign, int cpu, int Z, int N, int L,
+    hipStream_t stream)
+{
+    Line("numa_commit", stream).p("log_nodes", log_nodes)
+        .p("log_counts", log_counts).p("log_len", log_len)
+        .p("zone_free", zone_free).p("assign", assign).i("cpu", cpu)
+        .i("Z", Z).dims(N, g_R, -1).i("L", L);
+}
+
+void vamd_numa_revert(
+    const uint8_t* flag, const int* log_nodes, const int* log_len,
+    int* zone_free, int* assign, int cpu, int Z, int N, int L,
+    hipStream_t stream)
+{
+    Line("numa_revert", stream).p("flag", flag).p("log_nodes", log_nodes)
+        .p("log_len", log_len).p("zone_free", zone_free).p("assign", assign)
+        .i("cpu", cpu).i("Z", Z).dims(N, g_R, -1).i("L", L);
+}
+
 }  // extern "C"
 
 namespace {
@@ -379,8 +452,10 @@ struct ClassSpec {
     int ntasks;
     int min_needed = 0;
     int group = -1;      // domain-rule group, -1 = none
-    int mode = 0;        // 0 spread / 1 affinity / 2 anti
+    int mode = 0;        // 0 spread / 1 affinity / 2 anti / 3 hypernode
     int skew = 1;
+    int dev[3] = {0, 0, 0};   // count, memory, cores; count 0 = no request
+    int numa[2] = {0, 0};     // cpu millicores, policy; policy 0 = no request
 };
 
 struct Plan {
@@ -392,6 +467,8 @@ struct Plan {
     int G = 0, D = 4;
     bool mode_column = true;
     int null_one = -1;   // 0 class_group, 1 dom_of, 2 count, 3 scratch
+    // device-share and NUMA blocks (0 = the plan has none)
+    int K = 0, Z = 0;
 };
 
 void add_singles(Plan& p, int n, int ntasks = 2) {
@@ -520,6 +597,35 @@ void run(const char* name, const Plan& p, const char* mega = nullptr,
         queue_alloc, queue_limit, score, cap, log_nodes, log_counts, log_len,
         class_placed, job_placed, job_flag, sort_scratch,
         grp, skw, mod, dom_of, count, count_off, domains, dscratch};
+    if (p.K > 0) {
+        cy.card_mem_used = arr<int32_t>("card_mem_used", (size_t)p.K * N);
+        cy.card_cores_used = arr<int32_t>("card_cores_used", (size_t)p.K * N);
+        cy.card_state = arr<int32_t>("card_state", (size_t)p.K * N);
+        cy.card_mem_total = arr<int32_t>("card_mem_total", N);
+        auto* req = arr<int32_t>("class_dev_req", (size_t)C * 4);
+        cy.dev_assign = arr<int32_t>("dev_assign", (size_t)log_total * p.K);
+        cy.card_K = p.K;
+        int k = 0;
+        for (auto& j : p.jobs)
+            for (const ClassSpec& s : j) {
+                std::copy(s.dev, s.dev + 3, req + (size_t)k * 4);
+                ++k;
+            }
+        cy.class_dev_req = req;
+    }
+    if (p.Z > 0) {
+        cy.zone_free = arr<int32_t>("zone_free", (size_t)p.Z * N);
+        auto* req = arr<int32_t>("class_numa_req", (size_t)C * 2);
+        cy.numa_assign = arr<int32_t>("numa_assign", (size_t)log_total * p.Z);
+        cy.zone_Z = p.Z;
+        int k = 0;
+        for (auto& j : p.jobs)
+            for (const ClassSpec& s : j) {
+                std::copy(s.numa, s.numa + 2, req + (size_t)k * 2);
+                ++k;
+            }
+        cy.class_numa_req = req;
+    }
     if (vamd_run_cycle(&cy, STREAM) != 0) puts("vamd_run_cycle FAILED");
     flush_plan(header);
     cy.struct_size += 8;
@@ -532,6 +638,12 @@ ClassSpec spread(int ntasks, int g, int skew) {
 }
 ClassSpec affine(int ntasks, int g, int mode) {
     ClassSpec s{ntasks, 1}; s.group = g; s.mode = mode; return s;
+}
+ClassSpec with_dev(ClassSpec s, int count, int memory, int cores) {
+    s.dev[0] = count; s.dev[1] = memory; s.dev[2] = cores; return s;
+}
+ClassSpec with_numa(ClassSpec s, int cpu, int policy) {
+    s.numa[0] = cpu; s.numa[1] = policy; return s;
 }
 
 }  // namespace
@@ -694,5 +806,53 @@ int main(int argc, char** argv) {
         run("domain block dead, class_mode null", p);
     }
     puts("cycle trace done");
+
+    // ---- packed classes (device share, NUMA) ----------------------------------
+    // hypernode without a request first: mask, select, no count update
+    for (int N : {100, 5000}) {
+        Plan p; p.N = N; p.G = 2;
+        p.jobs = {{affine(3, 0, 3)}, {affine(600, 1, 3)},
+                  {affine(2, 1, 3), ClassSpec{2, 1}}};
+        run("hypernode classes", p);
+    }
+    // one packed class on each route; N = 100 would fuse a class without a
+    // request, so both sides of the shortcut are here
+    for (int N : {100, 5000}) {
+        Plan p; p.N = N; p.G = 2; p.K = 8; p.Z = 4;
+        p.jobs = {{with_dev(ClassSpec{3, 1}, 2, 1024, 25)},
+                  {with_dev(spread(4, 0, 2), 1, 0, 0)},
+                  {with_dev(affine(3, 1, 1), 1, 512, 0)},
+                  {with_dev(affine(3, 1, 2), 1, 0, 50)},
+                  {with_dev(affine(600, 0, 3), 4, 0, 0)},
+                  {with_numa(ClassSpec{3, 1}, 2000, 1)},
+                  {with_numa(ClassSpec{600, 1}, 500, 2)},
+                  {with_numa(spread(4, 1, 1), 1000, 1)},
+                  {with_numa(affine(2, 0, 1), 1000, 2)},
+                  {with_numa(affine(2, 1, 3), 250, 1)},
+                  {with_numa(with_dev(ClassSpec{5, 1}, 1, 2048, 10), 4000, 1)},
+                  {with_numa(with_dev(spread(5, 0, 1), 2, 0, 0), 4000, 2)},
+                  {ClassSpec{3, 1}},
+                  // multi-class jobs: every revert beside its packed one
+                  {with_dev(ClassSpec{2, 1}, 1, 100, 0),
+                   with_numa(spread(2, 0, 1), 1500, 1), ClassSpec{2, 0},
+                   with_numa(with_dev(affine(2, 1, 2), 1, 0, 0), 100, 2),
+                   with_numa(with_dev(affine(2, 0, 3), 3, 7, 9), 300, 1)}};
+        run("packed classes", p);
+        Plan d = p; d.Z = 0;
+        run("packed classes, NUMA block dead", d);
+        d = p; d.K = 0;
+        run("packed classes, device block dead", d);
+    }
+    {   // a packed class breaks a chain run and keeps a plan off the megacycle
+        Plan p; p.K = 2; p.Z = 2;
+        add_singles(p, 33);
+        p.jobs.push_back({with_dev(ClassSpec{2, 1}, 1, 10, 10)});
+        add_singles(p, 33);
+        p.jobs.push_back({with_numa(ClassSpec{2, 1}, 100, 2)});
+        add_singles(p, 33);
+        run("chain broken by packed classes", p, nullptr, "16");
+        run("megacycle with packed classes", p, "1");
+    }
+    puts("packed trace done");
     return 0;
 }

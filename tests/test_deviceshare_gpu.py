@@ -45,7 +45,8 @@ def test_device_cap(N, K, request_):
 
 
 @pytest.mark.parametrize("request_", dc.REQUESTS, ids=str)
-@pytest.mark.parametrize("L,K", [(1, 3), (4, 16), (5, 1), (67, 8)])
+@pytest.mark.parametrize("L,K", [(1, 3), (4, 16), (5, 1), (67, 8),
+                                 (4099, 16)])
 def test_device_commit_then_revert(L, K, request_):
     from volcano_amd.ops import hip
     case = dc.commit_case(L, K, request_, seed=L)

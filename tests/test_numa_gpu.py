@@ -43,7 +43,8 @@ def test_numa_cap(N, Z, cpu):
 
 @pytest.mark.parametrize("policy", [nc.HARD, nc.SOFT])
 @pytest.mark.parametrize("cpu", nc.CPUS)
-@pytest.mark.parametrize("L,Z", [(1, 2), (8, 8), (9, 3), (67, 8)])
+@pytest.mark.parametrize("L,Z", [(1, 2), (8, 8), (9, 3), (67, 8),
+                                 (8197, 8)])
 def test_numa_commit_then_revert(L, Z, cpu, policy):
     from volcano_amd.ops import hip
     case = nc.commit_case(L, Z, cpu, policy, seed=L)

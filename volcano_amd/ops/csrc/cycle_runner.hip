@@ -278,62 +278,46 @@ struct Runner {
                          v.job_placed, cy.N, cy.R, stream);
     }
 
-    // A class with a device or NUMA request: always the split path, the
-    // per-card and per-zone clamps right after the score so that every
-    // domain rule reads the clamped cap, the slices and zones taken after
-    // the select (and count update).  Only a hard NUMA policy clamps; a
-    // best-effort class pins what fits and leaves the rest unpinned.
-    void run_packed_class(const ClassView& v) const {
+    // One sequence for every class: score; the per-card and per-zone clamps
+    // of a device or NUMA request right after it, so that every domain rule
+    // reads the clamped cap (only a hard NUMA policy clamps; a best-effort
+    // class pins what fits and leaves the rest unpinned); the select its
+    // domain rule asks for; the slices and zones taken after the select
+    // (and count update).
+    void run_class(const ClassView& v) const {
+        if (v.group < 0 && v.dev == nullptr && v.numa == nullptr &&
+                v.cd.ntasks < BULK_TASKS && cy.N <= 4096) {
+            // small class on a small inventory, no rule and no request: ONE
+            // fused launch (score in-block + select).  At larger N the
+            // one-block score loses the multi-CU latency hiding of the
+            // grid-stride kernel (mix bench at N=10k measured 552 ms/step
+            // fused vs 334 ms split).
+            fused(v);
+            return;
+        }
         score(v);
         if (v.dev != nullptr) device_cap(v);
         if (v.numa != nullptr && v.numa[1] == NUMA_HARD) numa_cap(v);
         if (v.group >= 0 && v.mode == 0) {
+            // topology spread: eligibility moves with every single
+            // placement, so always the spread select, whatever the class
+            // size
             spread_select(v);
         } else {
+            // inter-pod affinity / keyed anti-affinity / network topology:
+            // the rule collapses into a mask over score/cap (from the
+            // group's live counts, or confining the class to the one
+            // hypernode chosen from the live cap), then the ordinary select
+            // (bulk by size) — a launch count constant in ntasks
             if (v.group >= 0) domain_mask(v);
             select(v);
+            // a hypernode group's slice is a read-only table: no count
+            // update follows
             if (v.group >= 0 && v.mode != MODE_HYPERNODE)
                 domain_count_add(v);
         }
         if (v.dev != nullptr) device_commit(v);
         if (v.numa != nullptr) numa_commit(v);
-    }
-
-    void run_class(const ClassView& v) const {
-        if (v.dev != nullptr || v.numa != nullptr) {
-            run_packed_class(v);
-        } else if (v.group >= 0 && v.mode == MODE_HYPERNODE) {
-            // network topology: the mask confines the class to the one
-            // hypernode chosen from the live cap; the group's slice is a
-            // read-only table, so no count update follows
-            score(v);
-            domain_mask(v);
-            select(v);
-        } else if (v.group >= 0 && v.mode != 0) {
-            // inter-pod affinity / keyed anti-affinity: the rule collapses
-            // into a mask over score/cap computed from the group's live
-            // counts, then the ordinary select (bulk by size) and one
-            // count update — four launches whatever ntasks is
-            score(v);
-            domain_mask(v);
-            select(v);
-            domain_count_add(v);
-        } else if (v.group >= 0) {
-            // topology spread: eligibility moves with every single
-            // placement — always score + spread select, whatever the
-            // class size
-            score(v);
-            spread_select(v);
-        } else if (v.cd.ntasks < BULK_TASKS && cy.N <= 4096) {
-            // small class on a small inventory: ONE fused launch (score
-            // in-block + select).  At larger N the one-block score loses
-            // the multi-CU latency hiding of the grid-stride kernel (mix
-            // bench at N=10k measured 552 ms/step fused vs 334 ms split).
-            fused(v);
-        } else {
-            score(v);
-            select(v);
-        }
     }
 
     // single-class jobs fuse the gang check into the commit (fuse_min)

@@ -1349,97 +1349,156 @@ __global__ void domain_count_add_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// Device share: per-card packing of GPU slices, per placement.
-//
-// Oracle: GPUDevicePool.allocate called once per pod (api/devices.py) —
-// each pod picks `count` slices best-fit: the fullest feasible card first
-// (mem_used larger wins, strictly), ties to the lower card index.  Two facts
-// make that closed-form, so nothing is simulated here:
-//   * capacity: a slice takes (memory, cores) from ONE card and cards are
-//     independent, so card k has a fixed number of slots for a request
-//     shape (card_slots); with S = sum of slots a node packs exactly
-//     floor(S / count) pods, whatever the order;
-//   * fill order: the chosen card only gets fuller, so it stays the strict
-//     maximum until it has no slot left; m pods in a row fill the cards in
-//     the order (mem_used desc, index asc) among cards with slots, each to
-//     its slot count, and pod i owns positions [i*count, (i+1)*count) of
+// Per-unit packing, per placement: a pod takes its request from the UNITS of
+// a node — GPU slices from cards (device share), CPU millicores from NUMA
+// zones (numaaware) — and the oracle picks a unit pod by pod with a strict
+// best-fit rule.  Two facts make that closed-form for every policy below, so
+// nothing is simulated here:
+//   * capacity: units are independent and unit u has a fixed number of slots
+//     for a request shape; with S = sum of slots and `need` slots per pod a
+//     node packs exactly floor(S / need) pods, whatever the order;
+//   * fill order: taking from the chosen unit moves it further towards the
+//     extreme the rule prefers, and moves no other unit, so it stays the
+//     strict choice until it has no slot left; m pods in a row fill the
+//     units in the order (key asc, index asc) among units with slots, each
+//     to its slot count, and pod i owns positions [i*need, (i+1)*need) of
 //     that sequence.
-// Card planes are int32 [K, N] (K <= 16 cards, card-major like the resource
-// planes: a wave reads 64 consecutive nodes of one card index); card_state
-// is the slice count with DS_GONE set for an exclusive or absent card.
-// mem_total < 2^28 (host-checked), so every product below fits int32 and
-// S <= 16 * 2^28 is summed in int64.
+// Unit planes are int32 [U, N] (unit-major like the resource planes: a wave
+// reads 64 consecutive nodes of one unit index), U <= WIDTH of the policy.
+// Every per-unit value is below 2^28 (host-checked), so a take fits
+// TAKE_BITS, the products below fit int32, and S <= 16 * 2^28 is summed in
+// int64.
+//
+// A policy is passed to the kernels by value and supplies only what differs:
+// WIDTH (lanes per log entry) and `units` (the live U); node_ctx + load (the
+// slots of one unit, with the loads they need, and its fill-order key when
+// asked for); apply (a take joins, dir = 1, or leaves, dir = -1, one unit);
+// need (slots per pod).
 // ---------------------------------------------------------------------------
-#define DS_MAX_CARDS 16
 #define DS_GONE (1 << 30)
-#define DS_TAKE_BITS 28
-#define DS_TAKE_MASK ((1u << DS_TAKE_BITS) - 1u)
-#define DS_THREADS 256
-#define DS_ENTRIES_PER_WAVE (WAVE / DS_MAX_CARDS)
+#define PACK_TAKE_BITS 28
+#define PACK_TAKE_MASK ((1u << PACK_TAKE_BITS) - 1u)
+#define PACK_THREADS 256
 
-// slots of one card for one slice shape (Card.fits, counted); the caller
-// has ruled out DS_GONE, and an exclusive request reads `state` alone
-DEVINL int card_slots(int mem_used, int cores_used, int state, int mem_total,
-                      int memory, int cores)
-{
-    if (memory == 0 && cores == 0) return state == 0 ? 1 : 0;
-    if (mem_used > mem_total) return 0;
-    int s = 0x7fffffff;
-    if (memory > 0) s = (mem_total - mem_used) / memory;
-    if (cores > 0) s = min(s, (100 - cores_used) / cores);
-    return max(s, 0);
-}
+struct PackUnit { int slots, key; };
 
-// `take` slices of the shape join (dir = 1) or leave (dir = -1) one card
-DEVINL void card_apply(int* __restrict__ mem_used, int* __restrict__ cores_used,
-                       int* __restrict__ state, size_t o, int take,
-                       int memory, int cores, int dir)
-{
-    int st = state[o];
-    if (memory == 0 && cores == 0) {
-        st = dir > 0 ? ((st + take) | DS_GONE) : ((st & ~DS_GONE) - take);
-    } else {
-        st += dir * take;
-        if (memory > 0) mem_used[o] += dir * take * memory;
-        if (cores > 0) cores_used[o] += dir * take * cores;
+// Device share.  Oracle: GPUDevicePool.allocate called once per pod
+// (api/devices.py) — each pod picks `count` slices best-fit: the fullest
+// feasible card first (mem_used larger wins, strictly), ties to the lower
+// card index.
+//   * slots: a slice takes (memory, cores) from ONE card, so card_slots is a
+//     function of that card alone.
+//   * order: the chosen card only gets fuller, so it stays the strict
+//     maximum.  The key is ~mem_used: a decreasing bijection of int32, so
+//     key asc is mem_used desc for EVERY int32 mem_used (nothing range-checks
+//     that plane; only mem_total < 2^28 is host-checked).
+// card_state is the slice count with DS_GONE set for an exclusive or absent
+// card.
+struct CardPolicy {
+    static constexpr int WIDTH = 16;
+    int* mem_used;
+    int* cores_used;
+    int* state;
+    const int* mem_total;       // [N]; unused by the revert
+    int count, memory, cores;
+    int units;
+
+    // a request the kernels cannot divide by or index with launches nothing
+    bool ok() const {
+        return count >= 1 && memory >= 0 && cores >= 0 && units >= 1 &&
+            units <= WIDTH;
     }
-    state[o] = st;
-}
+    DEVINL bool whole() const { return memory == 0 && cores == 0; }
+    DEVINL int need() const { return count; }
+    DEVINL int node_ctx(int node) const { return whole() ? 0 : mem_total[node]; }
 
-// After score_cap, before any domain rule: cap = min(cap, S / count), and
-// score = -inf where that leaves nothing (score > -inf <=> cap > 0 holds).
-// Grid-stride, one thread per node; a node with cap == 0 loads nothing.
-// The card loop is unrolled over the compile-time bound KB, so no card is
-// ever indexed dynamically in registers.
-template <int KB>
-__global__ void device_cap_kernel(
-    float* __restrict__ score, int* __restrict__ cap,
-    const int* __restrict__ card_mem_used,
-    const int* __restrict__ card_cores_used,
-    const int* __restrict__ card_state,
-    const int* __restrict__ card_mem_total,
-    int count, int memory, int cores, int K, int N)
+    // Card.fits, counted.  A DS_GONE card loads nothing else, and only the
+    // planes the shape is bound by (or the key needs) are loaded, both
+    // before the first division; an exclusive request reads `state` alone.
+    DEVINL PackUnit load(size_t o, int total, bool want_key) const {
+        PackUnit r = {0, 0};
+        const int st = state[o];
+        if (st & DS_GONE) return r;
+        const int mu = (want_key || !whole()) ? mem_used[o] : 0;
+        const int cu = cores > 0 ? cores_used[o] : 0;
+        r.key = ~mu;
+        if (whole()) {
+            r.slots = st == 0 ? 1 : 0;
+        } else if (mu <= total) {
+            int s = 0x7fffffff;
+            if (memory > 0) s = (total - mu) / memory;
+            if (cores > 0) s = min(s, (100 - cu) / cores);
+            r.slots = max(s, 0);
+        }
+        return r;
+    }
+
+    DEVINL void apply(size_t o, int take, int dir) const {
+        int st = state[o];
+        if (whole()) {
+            st = dir > 0 ? ((st + take) | DS_GONE) : ((st & ~DS_GONE) - take);
+        } else {
+            st += dir * take;
+            if (memory > 0) mem_used[o] += dir * take * memory;
+            if (cores > 0) cores_used[o] += dir * take * cores;
+        }
+        state[o] = st;
+    }
+};
+
+// Numaaware.  Oracle: NumaState.best_zone + take called once per pod
+// (scheduler/plugins/numaaware.py) — each pod takes its `cpu` millicores
+// from the zone with the SMALLEST free value that still fits (strictly
+// smaller wins, ties to the lower zone index).
+//   * slots: on integer millicores zone z has free_z / cpu of them, and a
+//     pod needs one.
+//   * order: the chosen zone only gets smaller, so it stays the strict
+//     minimum among fitting zones; the key is `free` itself.
+// free is 0 for the missing zones of a smaller node; 0 <= free < 2^28 and
+// cpu >= 1 (host-checked), so take * cpu never exceeds free.  A hard class
+// never logs more than S (the cap kernel clamped it); a best-effort class
+// may, and the surplus pods simply find no zone.
+struct ZonePolicy {
+    static constexpr int WIDTH = 8;
+    int* free;
+    int cpu;
+    int units;
+
+    // a request the kernels cannot divide by or index with launches nothing
+    bool ok() const { return cpu >= 1 && units >= 1 && units <= WIDTH; }
+    DEVINL int need() const { return 1; }
+    DEVINL int node_ctx(int) const { return 0; }
+    // branch-free, so the unrolled loads of the cap kernel stay independent
+    DEVINL PackUnit load(size_t o, int, bool) const {
+        const int f = free[o];
+        return {(int)((unsigned)max(f, 0) / (unsigned)cpu), f};
+    }
+    DEVINL void apply(size_t o, int take, int dir) const {
+        free[o] -= dir * take * cpu;
+    }
+};
+
+// After score_cap (cards before zones), before any domain rule:
+// cap = min(cap, S / need), and score = -inf where that leaves nothing
+// (score > -inf <=> cap > 0 holds).  Grid-stride, one thread per node; a
+// node with cap == 0 loads nothing.  The unit loop is unrolled over the
+// compile-time BOUND, so no unit is ever indexed dynamically in registers;
+// its loads are independent and issue back to back.
+template <class Policy, int BOUND>
+__global__ void pack_cap_kernel(
+    float* __restrict__ score, int* __restrict__ cap, const Policy p, int N)
 {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N;
          i += gridDim.x * blockDim.x) {
         const int c = cap[i];
         if (c <= 0) continue;
-        const bool whole = memory == 0 && cores == 0;
-        const int total = whole ? 0 : card_mem_total[i];
+        const int ctx = p.node_ctx(i);
         long long S = 0;
 #pragma unroll
-        for (int k = 0; k < KB; ++k) {
-            if (k < K) {
-                const size_t o = (size_t)k * N + i;
-                const int st = card_state[o];
-                if (st & DS_GONE) continue;
-                // only the planes the shape is bound by are loaded
-                const int mu = whole ? 0 : card_mem_used[o];
-                const int cu = cores > 0 ? card_cores_used[o] : 0;
-                S += card_slots(mu, cu, st, total, memory, cores);
-            }
-        }
-        const long long fit = S / count;
+        for (int u = 0; u < BOUND; ++u)
+            if (u < p.units)
+                S += p.load((size_t)u * N + i, ctx, false).slots;
+        const long long fit = S / p.need();
         if (fit < (long long)c) {
             cap[i] = (int)fit;
             if (fit == 0) score[i] = NEG_INF;
@@ -1447,249 +1506,95 @@ __global__ void device_cap_kernel(
     }
 }
 
-// After the select (and the domain count update): the logged placements
-// take their slices.  One 16-lane group per log entry (node, cnt), four
-// entries per wave, grid-stride over *log_len; lane k holds card k of the
-// entry's node.  rank = cards earlier in (mem_used desc, index asc) among
-// cards with slots, prefix = their slots, both by width-16 shuffles over
-// the 16 cards; take = clamp(cnt*count - prefix, 0, slots).  Each lane
-// updates its own card with plain stores and writes ONE word of the
-// entry's assignment row at position `rank`: card << 28 | take (cards
-// without a take fill the tail with 0).  A class logs a node at most once:
-// entries never share a card, so there are no atomics.  The loop bound is
-// the same for every lane of a wave — all 64 lanes stay active through the
-// shuffles.
-__global__ void __launch_bounds__(DS_THREADS) device_commit_kernel(
+// After the select (and the domain count update; cards before zones): the
+// logged placements take their slots.  One WIDTH-lane group per log entry
+// (node, cnt), WAVE / WIDTH entries per wave, grid-stride over *log_len;
+// lane u holds unit u of the entry's node.  Units with slots rank among
+// themselves in fill order, the rest follow by index: rank = units earlier
+// in that order, prefix = their slots, both by width-WIDTH shuffles;
+// take = clamp(cnt*need - prefix, 0, slots).  Each lane updates its own unit
+// with plain stores and writes ONE word of the entry's assignment row at
+// position `rank`: unit << 28 | take (0 without a take, which fills the
+// tail; the ranks of the lanes u < units are a permutation of 0..units-1).
+// A class logs a node at most once: entries never share a unit, so there
+// are no atomics.  The loop bound is the same for every lane of a wave —
+// all 64 lanes stay active through the shuffles, lanes u >= units and
+// entries e >= len with no slots.
+template <class Policy>
+__global__ void __launch_bounds__(PACK_THREADS) pack_commit_kernel(
     const int* __restrict__ log_nodes, const int* __restrict__ log_counts,
     const int* __restrict__ log_len,
-    int* __restrict__ card_mem_used, int* __restrict__ card_cores_used,
-    int* __restrict__ card_state, const int* __restrict__ card_mem_total,
-    int* __restrict__ assign,             // [L, K]
-    int count, int memory, int cores, int K, int N, int L)
+    int* __restrict__ assign,             // [L, units]
+    const Policy p, int N, int L)
 {
+    constexpr int W = Policy::WIDTH;
     int len = *log_len;
     if (len > L) len = L;
-    const int k = threadIdx.x & (DS_MAX_CARDS - 1);
-    const int group = (blockIdx.x * blockDim.x + threadIdx.x) / DS_MAX_CARDS;
-    const int sub = group & (DS_ENTRIES_PER_WAVE - 1);
-    const int groups = gridDim.x * blockDim.x / DS_MAX_CARDS;
+    const int u = threadIdx.x & (W - 1);
+    const int group = (blockIdx.x * blockDim.x + threadIdx.x) / W;
+    const int sub = group & (WAVE / W - 1);
+    const int groups = gridDim.x * blockDim.x / W;
     for (int base = group - sub; base < len; base += groups) {
         const int e = base + sub;
-        const bool row = e < len && k < K;
+        const bool row = e < len && u < p.units;
         int node = -1, cnt = 0;
         if (row) { node = log_nodes[e]; cnt = log_counts[e]; }
         const bool live = row && cnt > 0 && node >= 0 && node < N;
-        const size_t o = live ? (size_t)k * N + node : 0;
-        int mu = 0, slots = 0;
-        if (live) {
-            const int st = card_state[o];
-            if (!(st & DS_GONE)) {
-                mu = card_mem_used[o];
-                slots = card_slots(mu, cores > 0 ? card_cores_used[o] : 0, st,
-                                   card_mem_total[node], memory, cores);
-            }
-        }
-        // lanes with slots rank among themselves; the rest follow by index
+        const size_t o = live ? (size_t)u * N + node : 0;
+        PackUnit me = {0, 0};
+        if (live) me = p.load(o, p.node_ctx(node), true);
         int earlier = 0, with_slots = 0, empty_below = 0;
         long long prefix = 0;
 #pragma unroll
-        for (int j = 0; j < DS_MAX_CARDS; ++j) {
-            const int mu_j = __shfl(mu, j, DS_MAX_CARDS);
-            const int s_j = __shfl(slots, j, DS_MAX_CARDS);
+        for (int j = 0; j < W; ++j) {
+            const int key_j = __shfl(me.key, j, W);
+            const int s_j = __shfl(me.slots, j, W);
             const bool has = s_j > 0;
-            const bool first = has && (mu_j > mu || (mu_j == mu && j < k));
+            const bool first =
+                has && (key_j < me.key || (key_j == me.key && j < u));
             with_slots += has;
-            empty_below += !has && j < k;
+            empty_below += !has && j < u;
             earlier += first;
             prefix += first ? s_j : 0;
         }
-        const int rank = slots > 0 ? earlier : with_slots + empty_below;
-        long long t = (long long)cnt * count - prefix;
-        if (t > slots) t = slots;
+        const int rank = me.slots > 0 ? earlier : with_slots + empty_below;
+        long long t = (long long)cnt * p.need() - prefix;
+        if (t > me.slots) t = me.slots;
         const int take = t > 0 ? (int)t : 0;
-        if (take > 0)
-            card_apply(card_mem_used, card_cores_used, card_state, o, take,
-                       memory, cores, 1);
+        if (take > 0) p.apply(o, take, 1);
         if (row)
-            assign[(size_t)e * K + rank] = take > 0
-                ? (int)(((unsigned)k << DS_TAKE_BITS) | (unsigned)take) : 0;
+            assign[(size_t)e * p.units + rank] = take > 0
+                ? (int)(((unsigned)u << PACK_TAKE_BITS) | (unsigned)take) : 0;
     }
 }
 
 // Multi-class gang revert (beside cond_revert / spread_revert), gated on
-// the job flag: subtracts exactly what the assignment rows recorded and
-// zeroes them.  Same 16-lane groups; lane p owns position p of the row,
-// and the positions of a row name distinct cards.
-__global__ void __launch_bounds__(DS_THREADS) device_revert_kernel(
+// the job flag: gives back exactly what the assignment rows recorded and
+// zeroes them.  Same WIDTH-lane groups; lane pos owns position pos of the
+// row, and the positions of a row name distinct units.
+template <class Policy>
+__global__ void __launch_bounds__(PACK_THREADS) pack_revert_kernel(
     const uint8_t* __restrict__ flag, const int* __restrict__ log_nodes,
-    const int* __restrict__ log_len,
-    int* __restrict__ card_mem_used, int* __restrict__ card_cores_used,
-    int* __restrict__ card_state, int* __restrict__ assign,
-    int memory, int cores, int K, int N, int L)
+    const int* __restrict__ log_len, int* __restrict__ assign,
+    const Policy p, int N, int L)
 {
+    constexpr int W = Policy::WIDTH;
     if (*flag) return;
     int len = *log_len;
     if (len > L) len = L;
-    const int p = threadIdx.x & (DS_MAX_CARDS - 1);
-    if (p >= K) return;
-    const int groups = gridDim.x * blockDim.x / DS_MAX_CARDS;
-    for (int e = (blockIdx.x * blockDim.x + threadIdx.x) / DS_MAX_CARDS;
-         e < len; e += groups) {
-        const unsigned v = (unsigned)assign[(size_t)e * K + p];
+    const int pos = threadIdx.x & (W - 1);
+    if (pos >= p.units) return;
+    const int groups = gridDim.x * blockDim.x / W;
+    for (int e = (blockIdx.x * blockDim.x + threadIdx.x) / W; e < len;
+         e += groups) {
+        const unsigned v = (unsigned)assign[(size_t)e * p.units + pos];
         if (v == 0) continue;
-        assign[(size_t)e * K + p] = 0;
-        const int card = (int)(v >> DS_TAKE_BITS);
-        const int take = (int)(v & DS_TAKE_MASK);
+        assign[(size_t)e * p.units + pos] = 0;
+        const int unit = (int)(v >> PACK_TAKE_BITS);
+        const int take = (int)(v & PACK_TAKE_MASK);
         const int node = log_nodes[e];
-        if (take == 0 || card >= K || node < 0 || node >= N) continue;
-        card_apply(card_mem_used, card_cores_used, card_state,
-                   (size_t)card * N + node, take, memory, cores, -1);
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Numaaware: pinning CPU requests to NUMA zones, per placement.
-//
-// Oracle: NumaState.best_zone + take called once per pod
-// (scheduler/plugins/numaaware.py) — each pod takes its `cpu` millicores
-// from the zone with the SMALLEST free value that still fits (strictly
-// smaller wins, ties to the lower zone index).  On integer millicores two
-// facts make that closed-form, so nothing is simulated here:
-//   * capacity: zones are independent, zone z has free_z / cpu slots, and a
-//     node pins exactly S = sum of slots pods of the shape;
-//   * fill order: the chosen zone only gets smaller, so it stays the strict
-//     minimum among fitting zones until it has no slot left, and the other
-//     zones do not move; m pods in a row fill the zones in the order
-//     (free asc, index asc) among zones with slots, each to its slot count.
-// zone_free is int32 [Z, N] (Z <= 8 zones, zone-major like the resource and
-// card planes: a wave reads 64 consecutive nodes of one zone), 0 for the
-// missing zones of a smaller node.  0 <= free < 2^28 and cpu >= 1
-// (host-checked), so free << 3 | zone is a 31-bit sort key, take * cpu
-// never exceeds free, and S <= 8 * (2^28 - 1) is summed in int64.
-// ---------------------------------------------------------------------------
-#define NUMA_MAX_ZONES 8
-#define NUMA_TAKE_BITS 28
-#define NUMA_TAKE_MASK ((1u << NUMA_TAKE_BITS) - 1u)
-#define NUMA_THREADS 256
-#define NUMA_ENTRIES_PER_WAVE (WAVE / NUMA_MAX_ZONES)
-
-DEVINL int zone_slots(int free, int cpu) { return free > 0 ? free / cpu : 0; }
-
-// Hard policies, after score_cap (and device_cap), before any domain rule:
-// cap = min(cap, S), and score = -inf where that leaves nothing
-// (score > -inf <=> cap > 0 holds).  Grid-stride, one thread per node; a
-// node with cap == 0 loads nothing.  The zone loop is unrolled over the
-// compile-time bound ZB, so no zone is ever indexed dynamically in
-// registers; its loads are independent and issue back to back.
-template <int ZB>
-__global__ void numa_cap_kernel(
-    float* __restrict__ score, int* __restrict__ cap,
-    const int* __restrict__ zone_free, int cpu, int Z, int N)
-{
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N;
-         i += gridDim.x * blockDim.x) {
-        const int c = cap[i];
-        if (c <= 0) continue;
-        int free[ZB];
-#pragma unroll
-        for (int z = 0; z < ZB; ++z)
-            free[z] = z < Z ? zone_free[(size_t)z * N + i] : 0;
-        long long S = 0;
-#pragma unroll
-        for (int z = 0; z < ZB; ++z)
-            S += zone_slots(free[z], cpu);
-        if (S < (long long)c) {
-            cap[i] = (int)S;
-            if (S == 0) score[i] = NEG_INF;
-        }
-    }
-}
-
-// After the select (and count update, and device_commit): the logged
-// placements take their zones.  One 8-lane group per log entry (node, cnt),
-// eight entries per wave, grid-stride over *log_len; lane z holds zone z of
-// the entry's node.  A zone with slots carries the sort key free << 3 | z,
-// one without a key above all of those (bit 31 | z), so ONE unsigned
-// compare per peer gives both the fill order and the place of the unused
-// zones behind it: rank = keys below mine, prefix = their slots, both from
-// width-8 shuffles; take = clamp(cnt - prefix, 0, slots).  A hard class
-// never logs more than S (numa_cap clamped it); a best-effort class may, and
-// the surplus pods simply find no zone.  Each lane subtracts take * cpu from
-// its own zone with a plain store and writes ONE word of the entry's
-// assignment row at position `rank`: zone << 28 | take (0 without a take,
-// which fills the tail).  A class logs a node at most once: entries never
-// share a zone, so there are no atomics.  The loop bound is the same for
-// every lane of a wave — all 64 lanes stay active through the shuffles.
-__global__ void __launch_bounds__(NUMA_THREADS) numa_commit_kernel(
-    const int* __restrict__ log_nodes, const int* __restrict__ log_counts,
-    const int* __restrict__ log_len, int* __restrict__ zone_free,
-    int* __restrict__ assign,             // [L, Z]
-    int cpu, int Z, int N, int L)
-{
-    int len = *log_len;
-    if (len > L) len = L;
-    const int z = threadIdx.x & (NUMA_MAX_ZONES - 1);
-    const int group = (blockIdx.x * blockDim.x + threadIdx.x) / NUMA_MAX_ZONES;
-    const int sub = group & (NUMA_ENTRIES_PER_WAVE - 1);
-    const int groups = gridDim.x * blockDim.x / NUMA_MAX_ZONES;
-    for (int base = group - sub; base < len; base += groups) {
-        const int e = base + sub;
-        const bool row = e < len && z < Z;
-        int node = -1, cnt = 0;
-        if (row) { node = log_nodes[e]; cnt = log_counts[e]; }
-        const bool live = row && cnt > 0 && node >= 0 && node < N;
-        const size_t o = live ? (size_t)z * N + node : 0;
-        const int free = live ? zone_free[o] : 0;
-        const int slots = zone_slots(free, cpu);
-        const unsigned key = slots > 0
-            ? ((unsigned)free << 3) | (unsigned)z : 0x80000000u | (unsigned)z;
-        int rank = 0;
-        long long prefix = 0;
-#pragma unroll
-        for (int j = 0; j < NUMA_MAX_ZONES; ++j) {
-            const unsigned key_j = (unsigned)__shfl((int)key, j, NUMA_MAX_ZONES);
-            const int s_j = __shfl(slots, j, NUMA_MAX_ZONES);
-            const bool first = key_j < key;
-            rank += first;
-            prefix += first ? s_j : 0;
-        }
-        long long t = (long long)cnt - prefix;
-        if (t > slots) t = slots;
-        const int take = t > 0 ? (int)t : 0;
-        if (take > 0) zone_free[o] = free - take * cpu;
-        // lanes z >= Z rank behind every real zone: rank < Z exactly for row
-        if (row)
-            assign[(size_t)e * Z + rank] = take > 0
-                ? (int)(((unsigned)z << NUMA_TAKE_BITS) | (unsigned)take) : 0;
-    }
-}
-
-// Multi-class gang revert (beside cond_revert / spread_revert /
-// device_revert), gated on the job flag: gives back exactly what the
-// assignment rows recorded and zeroes them.  Same 8-lane groups; lane p
-// owns position p of the row, and the positions of a row name distinct
-// zones.
-__global__ void __launch_bounds__(NUMA_THREADS) numa_revert_kernel(
-    const uint8_t* __restrict__ flag, const int* __restrict__ log_nodes,
-    const int* __restrict__ log_len, int* __restrict__ zone_free,
-    int* __restrict__ assign, int cpu, int Z, int N, int L)
-{
-    if (*flag) return;
-    int len = *log_len;
-    if (len > L) len = L;
-    const int p = threadIdx.x & (NUMA_MAX_ZONES - 1);
-    if (p >= Z) return;
-    const int groups = gridDim.x * blockDim.x / NUMA_MAX_ZONES;
-    for (int e = (blockIdx.x * blockDim.x + threadIdx.x) / NUMA_MAX_ZONES;
-         e < len; e += groups) {
-        const unsigned v = (unsigned)assign[(size_t)e * Z + p];
-        if (v == 0) continue;
-        assign[(size_t)e * Z + p] = 0;
-        const int zone = (int)(v >> NUMA_TAKE_BITS);
-        const int take = (int)(v & NUMA_TAKE_MASK);
-        const int node = log_nodes[e];
-        if (zone >= Z || node < 0 || node >= N) continue;
-        zone_free[(size_t)zone * N + node] += take * cpu;
+        if (take == 0 || unit >= p.units || node < 0 || node >= N) continue;
+        p.apply((size_t)unit * N + node, take, -1);
     }
 }
 
@@ -2115,6 +2020,56 @@ select_chain_kernel(
 
 }  // namespace vamd
 
+// Per-unit packing: the launches behind the six vamd_device_* / vamd_numa_*
+// entry points (templates, so outside the C block).
+
+static int log_blocks(int L, int width)
+{
+    const int per_block = PACK_THREADS / width;
+    int blocks = min((L + per_block - 1) / per_block, 256);
+    return blocks < 1 ? 1 : blocks;
+}
+
+// the smallest unroll bound (WIDTH / 4, / 2, / 1) that holds p.units
+template <class Policy>
+static void launch_pack_cap(float* score, int* cap, const Policy& p, int N,
+                            hipStream_t stream)
+{
+    if (!p.ok()) return;
+    constexpr int W = Policy::WIDTH;
+    int threads = 256;
+    int blocks = min((N + threads - 1) / threads, 4096);
+    if (blocks < 1) blocks = 1;
+    auto* kernel = p.units <= W / 4 ? vamd::pack_cap_kernel<Policy, W / 4>
+        : p.units <= W / 2 ? vamd::pack_cap_kernel<Policy, W / 2>
+        : vamd::pack_cap_kernel<Policy, W>;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, stream, score,
+                       cap, p, N);
+}
+
+template <class Policy>
+static void launch_pack_commit(
+    const int* log_nodes, const int* log_counts, const int* log_len,
+    int* assign, const Policy& p, int N, int L, hipStream_t stream)
+{
+    if (!p.ok()) return;
+    hipLaunchKernelGGL(vamd::pack_commit_kernel<Policy>,
+                       dim3(log_blocks(L, Policy::WIDTH)), dim3(PACK_THREADS),
+                       0, stream, log_nodes, log_counts, log_len, assign, p,
+                       N, L);
+}
+
+template <class Policy>
+static void launch_pack_revert(
+    const uint8_t* flag, const int* log_nodes, const int* log_len,
+    int* assign, const Policy& p, int N, int L, hipStream_t stream)
+{
+    if (!p.ok()) return;
+    hipLaunchKernelGGL(vamd::pack_revert_kernel<Policy>,
+                       dim3(log_blocks(L, Policy::WIDTH)), dim3(PACK_THREADS),
+                       0, stream, flag, log_nodes, log_len, assign, p, N, L);
+}
+
 // ---------------------------------------------------------------------------
 // C ABI launchers (bound in bindings.cpp; stream passed from torch)
 // ---------------------------------------------------------------------------
@@ -2260,21 +2215,7 @@ void vamd_domain_count_add(
                        log_len, dom_of, dom_count, D, N, K);
 }
 
-int vamd_device_max_cards(void) { return DS_MAX_CARDS; }
-
-// a request the kernels cannot divide by or index with launches nothing
-static bool device_shape_ok(int count, int memory, int cores, int K)
-{
-    return count >= 1 && memory >= 0 && cores >= 0 && K >= 1 &&
-        K <= DS_MAX_CARDS;
-}
-
-static int device_log_blocks(int L)
-{
-    const int per_block = DS_THREADS / DS_MAX_CARDS;
-    int blocks = min((L + per_block - 1) / per_block, 256);
-    return blocks < 1 ? 1 : blocks;
-}
+int vamd_device_max_cards(void) { return vamd::CardPolicy::WIDTH; }
 
 void vamd_device_cap(
     float* score, int* cap, const int* card_mem_used,
@@ -2282,19 +2223,10 @@ void vamd_device_cap(
     const int* card_mem_total, int count, int memory, int cores, int K,
     int N, hipStream_t stream)
 {
-    if (!device_shape_ok(count, memory, cores, K)) return;
-    int threads = 256;
-    int blocks = min((N + threads - 1) / threads, 4096);
-    if (blocks < 1) blocks = 1;
-#define VAMD_DEVICE_CAP(KB)                                                  \
-    hipLaunchKernelGGL(vamd::device_cap_kernel<KB>, dim3(blocks),            \
-                       dim3(threads), 0, stream, score, cap, card_mem_used,  \
-                       card_cores_used, card_state, card_mem_total, count,   \
-                       memory, cores, K, N)
-    if (K <= 4) VAMD_DEVICE_CAP(4);
-    else if (K <= 8) VAMD_DEVICE_CAP(8);
-    else VAMD_DEVICE_CAP(16);
-#undef VAMD_DEVICE_CAP
+    // the cap kernel only loads from the planes
+    launch_pack_cap(score, cap, vamd::CardPolicy{
+        (int*)card_mem_used, (int*)card_cores_used, (int*)card_state,
+        card_mem_total, count, memory, cores, K}, N, stream);
 }
 
 void vamd_device_commit(
@@ -2303,11 +2235,10 @@ void vamd_device_commit(
     const int* card_mem_total, int* assign, int count, int memory, int cores,
     int K, int N, int L, hipStream_t stream)
 {
-    if (!device_shape_ok(count, memory, cores, K)) return;
-    hipLaunchKernelGGL(vamd::device_commit_kernel, dim3(device_log_blocks(L)),
-                       dim3(DS_THREADS), 0, stream, log_nodes, log_counts,
-                       log_len, card_mem_used, card_cores_used, card_state,
-                       card_mem_total, assign, count, memory, cores, K, N, L);
+    launch_pack_commit(log_nodes, log_counts, log_len, assign,
+                       vamd::CardPolicy{card_mem_used, card_cores_used,
+                                        card_state, card_mem_total, count,
+                                        memory, cores, K}, N, L, stream);
 }
 
 void vamd_device_revert(
@@ -2315,43 +2246,20 @@ void vamd_device_revert(
     int* card_mem_used, int* card_cores_used, int* card_state, int* assign,
     int memory, int cores, int K, int N, int L, hipStream_t stream)
 {
-    if (!device_shape_ok(1, memory, cores, K)) return;
-    hipLaunchKernelGGL(vamd::device_revert_kernel, dim3(device_log_blocks(L)),
-                       dim3(DS_THREADS), 0, stream, flag, log_nodes, log_len,
-                       card_mem_used, card_cores_used, card_state, assign,
-                       memory, cores, K, N, L);
+    launch_pack_revert(flag, log_nodes, log_len, assign,
+                       vamd::CardPolicy{card_mem_used, card_cores_used,
+                                        card_state, nullptr, 1, memory, cores,
+                                        K}, N, L, stream);
 }
 
-int vamd_numa_max_zones(void) { return NUMA_MAX_ZONES; }
-
-// a request the kernels cannot divide by or index with launches nothing
-static bool numa_shape_ok(int cpu, int Z)
-{
-    return cpu >= 1 && Z >= 1 && Z <= NUMA_MAX_ZONES;
-}
-
-static int numa_log_blocks(int L)
-{
-    const int per_block = NUMA_THREADS / NUMA_MAX_ZONES;
-    int blocks = min((L + per_block - 1) / per_block, 256);
-    return blocks < 1 ? 1 : blocks;
-}
+int vamd_numa_max_zones(void) { return vamd::ZonePolicy::WIDTH; }
 
 void vamd_numa_cap(float* score, int* cap, const int* zone_free, int cpu,
                    int Z, int N, hipStream_t stream)
 {
-    if (!numa_shape_ok(cpu, Z)) return;
-    int threads = 256;
-    int blocks = min((N + threads - 1) / threads, 4096);
-    if (blocks < 1) blocks = 1;
-#define VAMD_NUMA_CAP(ZB)                                                    \
-    hipLaunchKernelGGL(vamd::numa_cap_kernel<ZB>, dim3(blocks),              \
-                       dim3(threads), 0, stream, score, cap, zone_free, cpu, \
-                       Z, N)
-    if (Z <= 2) VAMD_NUMA_CAP(2);
-    else if (Z <= 4) VAMD_NUMA_CAP(4);
-    else VAMD_NUMA_CAP(8);
-#undef VAMD_NUMA_CAP
+    // the cap kernel only loads from the plane
+    launch_pack_cap(score, cap, vamd::ZonePolicy{(int*)zone_free, cpu, Z}, N,
+                    stream);
 }
 
 void vamd_numa_commit(
@@ -2359,10 +2267,8 @@ void vamd_numa_commit(
     int* zone_free, int* assign, int cpu, int Z, int N, int L,
     hipStream_t stream)
 {
-    if (!numa_shape_ok(cpu, Z)) return;
-    hipLaunchKernelGGL(vamd::numa_commit_kernel, dim3(numa_log_blocks(L)),
-                       dim3(NUMA_THREADS), 0, stream, log_nodes, log_counts,
-                       log_len, zone_free, assign, cpu, Z, N, L);
+    launch_pack_commit(log_nodes, log_counts, log_len, assign,
+                       vamd::ZonePolicy{zone_free, cpu, Z}, N, L, stream);
 }
 
 void vamd_numa_revert(
@@ -2370,10 +2276,8 @@ void vamd_numa_revert(
     int* zone_free, int* assign, int cpu, int Z, int N, int L,
     hipStream_t stream)
 {
-    if (!numa_shape_ok(cpu, Z)) return;
-    hipLaunchKernelGGL(vamd::numa_revert_kernel, dim3(numa_log_blocks(L)),
-                       dim3(NUMA_THREADS), 0, stream, flag, log_nodes, log_len,
-                       zone_free, assign, cpu, Z, N, L);
+    launch_pack_revert(flag, log_nodes, log_len, assign,
+                       vamd::ZonePolicy{zone_free, cpu, Z}, N, L, stream);
 }
 
 void vamd_batch_score(const VamdCycle& cy, const VamdDevDescs& dd, int c0,

@@ -106,19 +106,26 @@ void vamd_domain_count_add(
     const int* dom_of, int* dom_count, int D, int N, int K,
     hipStream_t stream);
 
-// --- device share: per-card packing of GPU slices --------------------------
+// --- per-unit packing: GPU slices on cards, CPU requests on NUMA zones ------
 //
-// Card planes are int32 [K, N] (card-major), K <= vamd_device_max_cards():
+// A pod takes its request from the units of a node; the rule is the host's
+// own, once per pod, computed in closed form: a unit has a fixed number of
+// slots for a request, a node packs sum(slots) / need pods, and pods in a
+// row fill the units in a strict order among units with slots, each to its
+// slot count.  Unit planes are int32 [U, N] (unit-major).  A commit records
+// what it took in assign[L, U], parallel to the log: the used units of
+// entry e in fill order, unit << 28 | take; the tail is 0.
+//
+// The six launchers are weak: a program that links the runner alone leaves
+// both blocks of VamdCycle unset and never calls them.
+//
+// Device share.  Card planes [K, N], K <= vamd_device_max_cards():
 // card_mem_used, card_cores_used (percent) and card_state = slice count,
 // with VAMD_CARD_GONE set for an exclusive or absent card;
 // card_mem_total[N] < 2^28.  A request is (count slices, memory per slice,
 // cores per slice); memory == 0 && cores == 0 asks for whole cards.  The
-// rule is GPUDevicePool.allocate once per pod (best fit: fullest feasible
-// card first, ties to the lower index), computed in closed form.
-//
-// The three launchers are weak: a program that links the runner alone
-// (the dispatch trace) never sets the device-share block and never calls
-// them.
+// rule is GPUDevicePool.allocate (best fit: fullest feasible card first,
+// ties to the lower index).
 #define VAMD_CARD_GONE (1 << 30)
 
 // After vamd_score_cap, before any domain rule: cap = min(cap, S / count)
@@ -131,8 +138,8 @@ __attribute__((weak)) void vamd_device_cap(
 
 // After the select: entry e < *log_len (<= L) of the log takes
 // log_counts[e] * count slices on node log_nodes[e], cards in the order
-// (mem_used desc, index asc) among cards with slots.  assign[L, K]: the
-// used cards of entry e in that order, card << 28 | take; the tail is 0.
+// (mem_used desc, index asc) among cards with slots, recorded in
+// assign[L, K].
 __attribute__((weak)) void vamd_device_commit(
     const int* log_nodes, const int* log_counts, const int* log_len,
     int* card_mem_used, int* card_cores_used, int* card_state,
@@ -149,17 +156,12 @@ __attribute__((weak)) void vamd_device_revert(
 // Largest K of the card planes.
 __attribute__((weak)) int vamd_device_max_cards(void);
 
-// --- numaaware: pinning CPU requests to NUMA zones -------------------------
-//
-// zone_free is an int32 plane [Z, N] (zone-major), Z <= vamd_numa_max_zones():
+// Numaaware.  zone_free is one plane [Z, N], Z <= vamd_numa_max_zones():
 // free millicores of zone z of node n, 0 <= free < 2^28, 0 for the missing
 // zones of a smaller node.  A request is `cpu` >= 1 millicores that must
-// come from ONE zone.  The rule is NumaState.best_zone / take once per pod
-// (the smallest zone that still fits, ties to the lower index), computed in
-// closed form: zone z has free / cpu slots, zones fill in the order
-// (free asc, index asc) among zones with slots.
-//
-// The three launchers are weak, like the device-share ones.
+// come from ONE zone: zone z has free / cpu slots.  The rule is
+// NumaState.best_zone / take (the smallest zone that still fits, ties to
+// the lower index): zones fill in the order (free asc, index asc).
 
 // Hard policies only, after vamd_score_cap (and vamd_device_cap), before any
 // domain rule: cap = min(cap, S) with S the node's slots; score = -inf
@@ -170,8 +172,7 @@ __attribute__((weak)) void vamd_numa_cap(
 
 // After the select: the first min(log_counts[e], S) pods of entry
 // e < *log_len (<= L) take a zone each on node log_nodes[e]; the rest stay
-// unpinned.  assign[L, Z]: the used zones of entry e in fill order,
-// zone << 28 | take; the tail is 0.
+// unpinned; recorded in assign[L, Z].
 __attribute__((weak)) void vamd_numa_commit(
     const int* log_nodes, const int* log_counts, const int* log_len,
     int* zone_free, int* assign, int cpu, int Z, int N, int L,

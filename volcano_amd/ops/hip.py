@@ -310,19 +310,42 @@ def domain_count_add(log_nodes, log_counts, log_len, dom_of, dom_count):
         _p(dom_count), c_int(D), c_int(N), c_int(K), _stream())
 
 
-def _card_planes(op, mem_used, cores_used, state, mem_total):
-    """(K, N) of a set of card planes, checked."""
-    if mem_used.dim() != 2 or not 1 <= mem_used.shape[0] <= DEV_MAX_CARDS:
-        raise ValueError(f"{op}: card planes are [K, N], "
-                         f"1 <= K <= {DEV_MAX_CARDS}")
-    K, N = mem_used.shape
-    if cores_used.shape != (K, N) or state.shape != (K, N) \
-            or mem_total.shape != (N,):
-        raise ValueError(f"{op}: card planes differ in shape")
-    for t in (mem_used, cores_used, state, mem_total):
+# what a set of unit planes allows and how each family words its three
+# complaints: (limit on U, wrong rank or U, shapes differ, wrong layout)
+_CARDS = (DEV_MAX_CARDS,
+          f"card planes are [K, N], 1 <= K <= {DEV_MAX_CARDS}",
+          "card planes differ in shape", "card planes are contiguous int32")
+_ZONES = (NUMA_MAX_ZONES,) + 3 * (
+    f"zone_free is contiguous int32 [Z, N], 1 <= Z <= {NUMA_MAX_ZONES}",)
+
+
+def _unit_planes(op, family, planes, per_node=None):
+    """(U, N) of the unit planes of a family, checked: contiguous int32
+    [U, N], 1 <= U <= limit, all the same shape (``per_node``: [N]).
+    Plain loops: this runs in front of every launch."""
+    limit, bad_rank, bad_shape, bad_layout = family
+    shape = planes[0].shape
+    if len(shape) != 2 or not 1 <= shape[0] <= limit:
+        raise ValueError(f"{op}: {bad_rank}")
+    for t in planes:
+        if t.shape != shape:
+            raise ValueError(f"{op}: {bad_shape}")
+    if per_node is not None:
+        if per_node.shape != shape[1:]:
+            raise ValueError(f"{op}: {bad_shape}")
+        planes += (per_node,)
+    for t in planes:
         if t.dtype != torch.int32 or not t.is_contiguous():
-            raise ValueError(f"{op}: card planes are contiguous int32")
-    return K, N
+            raise ValueError(f"{op}: {bad_layout}")
+    return shape
+
+
+def _assign_rows(op, assign, L, U, dims):
+    """``assign`` is contiguous int32 [L, U]; ``dims`` words the shape."""
+    if assign.shape != (L, U) or assign.dtype != torch.int32 \
+            or not assign.is_contiguous():
+        raise ValueError(f"{op}: assign is contiguous int32 {dims}, "
+                         "parallel to the log")
 
 
 def device_cap(score, cap, mem_used, cores_used, state, mem_total, request):
@@ -332,7 +355,8 @@ def device_cap(score, cap, mem_used, cores_used, state, mem_total, request):
     ``score = -inf`` where that leaves 0.  Both change in place."""
     lib = _load()
     count, memory, cores = check_device_request(request)
-    K, N = _card_planes("device_cap", mem_used, cores_used, state, mem_total)
+    K, N = _unit_planes("device_cap", _CARDS, (mem_used, cores_used, state),
+                        mem_total)
     if score.shape != (N,) or cap.shape != (N,):
         raise ValueError("device_cap: score and cap need one entry per node")
     lib.vamd_device_cap(
@@ -348,13 +372,12 @@ def device_commit(log_nodes, log_counts, log_len, mem_used, cores_used, state,
     cards in fill order as ``card << 28 | take``."""
     lib = _load()
     count, memory, cores = check_device_request(request)
-    K, N = _card_planes("device_commit", mem_used, cores_used, state,
+    K, N = _unit_planes("device_commit", _CARDS, (mem_used, cores_used, state),
                         mem_total)
     L = log_nodes.shape[0]
-    if log_counts.shape[0] != L or assign.shape != (L, K) \
-            or assign.dtype != torch.int32 or not assign.is_contiguous():
-        raise ValueError("device_commit: assign is contiguous int32 [L, K], "
-                         "parallel to the log")
+    # a log_counts of another length gets the same complaint
+    _assign_rows("device_commit", assign,
+                 L if log_counts.shape[0] == L else -1, K, "[L, K]")
     lib.vamd_device_commit(
         _p(log_nodes), _p(log_counts), _p(log_len), _p(mem_used),
         _p(cores_used), _p(state), _p(mem_total), _p(assign), c_int(count),
@@ -367,34 +390,14 @@ def device_revert(flag, log_nodes, log_len, mem_used, cores_used, state,
     recorded, and ``assign`` is zeroed."""
     lib = _load()
     _, memory, cores = check_device_request(request)
-    K, N = _card_planes("device_revert", mem_used, cores_used, state,
+    K, N = _unit_planes("device_revert", _CARDS, (mem_used, cores_used, state),
                         mem_total)
     L = log_nodes.shape[0]
-    if assign.shape != (L, K) or assign.dtype != torch.int32 \
-            or not assign.is_contiguous():
-        raise ValueError("device_revert: assign is contiguous int32 [L, K], "
-                         "parallel to the log")
+    _assign_rows("device_revert", assign, L, K, "[L, K]")
     lib.vamd_device_revert(
         _p(flag), _p(log_nodes), _p(log_len), _p(mem_used), _p(cores_used),
         _p(state), _p(assign), c_int(memory), c_int(cores), c_int(K),
         c_int(N), c_int(L), _stream())
-
-
-def _zone_plane(op, zone_free):
-    """(Z, N) of a zone plane, checked."""
-    if zone_free.dim() != 2 or not 1 <= zone_free.shape[0] <= NUMA_MAX_ZONES \
-            or zone_free.dtype != torch.int32 \
-            or not zone_free.is_contiguous():
-        raise ValueError(f"{op}: zone_free is contiguous int32 [Z, N], "
-                         f"1 <= Z <= {NUMA_MAX_ZONES}")
-    return zone_free.shape
-
-
-def _zone_rows(op, assign, L, Z):
-    if assign.shape != (L, Z) or assign.dtype != torch.int32 \
-            or not assign.is_contiguous():
-        raise ValueError(f"{op}: assign is contiguous int32 [L, Z], "
-                         "parallel to the log")
 
 
 def numa_cap(score, cap, zone_free, cpu):
@@ -404,7 +407,7 @@ def numa_cap(score, cap, zone_free, cpu):
     ``score = -inf`` where that leaves 0.  Both change in place."""
     lib = _load()
     cpu, _ = check_numa_request(cpu, 1)
-    Z, N = _zone_plane("numa_cap", zone_free)
+    Z, N = _unit_planes("numa_cap", _ZONES, (zone_free,))
     if score.shape != (N,) or cap.shape != (N,):
         raise ValueError("numa_cap: score and cap need one entry per node")
     lib.vamd_numa_cap(_p(score), _p(cap), _p(zone_free), c_int(cpu), c_int(Z),
@@ -418,11 +421,11 @@ def numa_commit(log_nodes, log_counts, log_len, zone_free, assign, cpu):
     ``zone << 28 | take``."""
     lib = _load()
     cpu, _ = check_numa_request(cpu, 1)
-    Z, N = _zone_plane("numa_commit", zone_free)
+    Z, N = _unit_planes("numa_commit", _ZONES, (zone_free,))
     L = log_nodes.shape[0]
     if log_counts.shape[0] != L:
         raise ValueError("numa_commit: log_nodes and log_counts differ")
-    _zone_rows("numa_commit", assign, L, Z)
+    _assign_rows("numa_commit", assign, L, Z, "[L, Z]")
     lib.vamd_numa_commit(
         _p(log_nodes), _p(log_counts), _p(log_len), _p(zone_free), _p(assign),
         c_int(cpu), c_int(Z), c_int(N), c_int(L), _stream())
@@ -433,9 +436,9 @@ def numa_revert(flag, log_nodes, log_len, zone_free, assign, cpu):
     and ``assign`` is zeroed."""
     lib = _load()
     cpu, _ = check_numa_request(cpu, 1)
-    Z, N = _zone_plane("numa_revert", zone_free)
+    Z, N = _unit_planes("numa_revert", _ZONES, (zone_free,))
     L = log_nodes.shape[0]
-    _zone_rows("numa_revert", assign, L, Z)
+    _assign_rows("numa_revert", assign, L, Z, "[L, Z]")
     lib.vamd_numa_revert(
         _p(flag), _p(log_nodes), _p(log_len), _p(zone_free), _p(assign),
         c_int(cpu), c_int(Z), c_int(N), c_int(L), _stream())
@@ -548,9 +551,9 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
                 raise ValueError("run_cycle: group_row must be int32 [G]")
             cy.group_row = rows.ctypes.data
     if devices is not None:
-        K, _ = _card_planes("run_cycle", devices["mem_used"],
-                            devices["cores_used"], devices["state"],
-                            devices["mem_total"])
+        K, _ = _unit_planes("run_cycle", _CARDS, (
+            devices["mem_used"], devices["cores_used"], devices["state"]),
+            devices["mem_total"])
         creq = devices["class_req"]
         if creq.shape != (n_classes, 4) or creq.dtype != "int32" \
                 or not creq.flags["C_CONTIGUOUS"]:
@@ -558,8 +561,8 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
                              "[C, 4]")
         for row in creq[creq[:, 0] > 0]:
             check_device_request(row[:3])
-        if devices["assign"].shape != (log_nodes.shape[0], K):
-            raise ValueError("run_cycle: devices.assign must be [L, K]")
+        _assign_rows("run_cycle", devices["assign"], log_nodes.shape[0], K,
+                     "[L, K]")
         cy.card_mem_used = _addr(devices["mem_used"])
         cy.card_cores_used = _addr(devices["cores_used"])
         cy.card_state = _addr(devices["state"])
@@ -568,7 +571,7 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
         cy.dev_assign = _addr(devices["assign"])
         cy.card_K = K
     if numa is not None:
-        Z, zn = _zone_plane("run_cycle", numa["zone_free"])
+        Z, zn = _unit_planes("run_cycle", _ZONES, (numa["zone_free"],))
         nreq = numa["class_req"]
         if zn != N or nreq.shape != (n_classes, 2) \
                 or nreq.dtype != "int32" or not nreq.flags["C_CONTIGUOUS"]:
@@ -576,7 +579,8 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
                              "numa.class_req int32 [C, 2]")
         for row in nreq[nreq[:, 1] != 0]:
             check_numa_request(*row)
-        _zone_rows("run_cycle", numa["assign"], log_nodes.shape[0], Z)
+        _assign_rows("run_cycle", numa["assign"], log_nodes.shape[0], Z,
+                     "[L, Z]")
         cy.zone_free = _addr(numa["zone_free"])
         cy.class_numa_req = nreq.ctypes.data
         cy.numa_assign = _addr(numa["assign"])
