@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 import _kernel_cases as kc
+from _plan_spy import plans_of
 from volcano_amd.ops import reference as ref
 
 # (count, memory, cores): memory-bound, cores-bound, memory == 0 with cores,
@@ -78,8 +79,6 @@ def run_cluster(exact):
     from volcano_amd.scheduler import (FakeBinder, Scheduler, SchedulerCache,
                                        default_config)
     from volcano_amd.scheduler.config import PluginOption
-    from volcano_amd.scheduler import plan as planmod
-    import volcano_amd.scheduler.actions.allocate as alloc
     from volcano_amd.store import ObjectStore
     from volcano_amd.utils import synth
     GI = 1024 ** 3
@@ -108,19 +107,9 @@ def run_cluster(exact):
                                  mem=GI, priority=prio)
             pod.meta.annotations.update(ann)
             store.create("Pod", pod)
-    plans = []
-    real = planmod.run_plan_torch
-
-    def spy(plan):
-        plans.append([(cp.job_key, cp.ntasks, getattr(cp, "device", None),
-                       cp.forbid.tolist()) for cp in plan.classes])
-        return real(plan)
-
-    alloc.run_plan_torch = spy
-    try:
-        sched.run_once()
-    finally:
-        alloc.run_plan_torch = real
+    plans = [[(cp.job_key, cp.ntasks, getattr(cp, "device", None),
+               cp.forbid.tolist()) for cp in plan.classes]
+             for plan in plans_of(sched)]
     anns = {k.split("/")[1]: dict(t.pod.meta.annotations)
             for job in cache.jobs.values() for k, t in job.tasks.items()}
     binds = {k.split("/")[1]: v for k, v in binder.binds.items()}

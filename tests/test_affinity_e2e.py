@@ -7,6 +7,7 @@ from collections import Counter
 
 import pytest
 
+from _plan_spy import plans_of
 from volcano_amd.scheduler import (FakeBinder, Scheduler, SchedulerCache,
                                    default_config)
 from volcano_amd.scheduler.config import PluginOption, Tier
@@ -88,26 +89,6 @@ def node_counts(binder, prefix=""):
                    if key.startswith(f"default/{prefix}"))
 
 
-def _plans_of(sched):
-    """Run one cycle, returning the plans the torch runner was given."""
-    from volcano_amd.scheduler import plan as planmod
-    import volcano_amd.scheduler.actions.allocate as alloc
-    seen = []
-    real = planmod.run_plan_torch
-
-    def spy(plan):
-        seen.append(plan)
-        return real(plan)
-
-    orig = alloc.run_plan_torch
-    alloc.run_plan_torch = spy
-    try:
-        sched.run_once()
-    finally:
-        alloc.run_plan_torch = orig
-    return seen
-
-
 def best_zone(store_sizes):
     """Zone of the node a single unconstrained pod lands on."""
     store, binder, sched = mk(exact=None)
@@ -123,7 +104,7 @@ def test_six_zone_affine_replicas_one_cycle():
     store, binder, sched = mk(exact=True)
     zones = inventory(store, SMALL)
     job(store, "web", 6, 1)
-    plans = _plans_of(sched)
+    plans = plans_of(sched)
     c = zone_counts(binder, zones)
     assert sum(c.values()) == 6
     assert len(c) == 1, c
@@ -153,7 +134,7 @@ def _hostname_four(exact, key):
     inventory(store, FOUR)
     job(store, "web-a", 2, 2, key=key, priority=10)
     job(store, "web-b", 2, 2, key=key, priority=0, cpu=400)
-    plans = _plans_of(sched)
+    plans = plans_of(sched)
     return node_counts(binder), plans[0]
 
 
@@ -217,7 +198,7 @@ def test_gang_revert_gives_the_domain_back():
     zones = inventory(store, SMALL)
     job(store, "gang", 8, 8, priority=10)
     job(store, "later", 2, 1, priority=0)
-    plans = _plans_of(sched)
+    plans = plans_of(sched)
     assert not any(k.startswith("default/gang") for k in binder.binds)
     c = zone_counts(binder, zones, "later")
     assert c == Counter({best_zone(SMALL): 2}), c
@@ -252,7 +233,7 @@ def _anti_after_one_cycle(exact):
     sched.run_once()
     taken = zones[binder.binds["default/first-w-0"]]
     job(store, "rest", 3, 1, kind="podAntiAffinity")
-    plans = _plans_of(sched)
+    plans = plans_of(sched)
     return taken, zone_counts(binder, zones, "rest"), plans[0]
 
 
@@ -279,7 +260,7 @@ def test_keyed_anti_affinity_one_per_zone():
     store, binder, sched = mk(exact=True)
     zones = inventory(store, ANTI4)
     job(store, "web", 5, 1, kind="podAntiAffinity")
-    plans = _plans_of(sched)
+    plans = plans_of(sched)
     c = zone_counts(binder, zones)
     assert c == Counter({"a": 1, "b": 1, "c": 1}), c
     cp = plans[0].classes[0]
@@ -309,7 +290,7 @@ def test_affinity_wins_over_keyed_anti_affinity_on_one_class():
     sched.run_once()
     job(store, "web", 2, 1, extra={"podAntiAffinity": {
         "group": "rack", "topologyKey": "zone"}})
-    plan = _plans_of(sched)[0]
+    plan = plans_of(sched)[0]
     cp = plan.classes[0]
     assert cp.affinity is not None and cp.affinity[1] == 1
     assert any(int(w) for w in cp.forbid)
@@ -334,7 +315,7 @@ def test_zone_affinity_with_hostname_anti_affinity():
     zones = inventory(store, SMALL)
     job(store, "web", 5, 1,
         extra={"podAntiAffinity": {"group": "web-host"}})
-    plans = _plans_of(sched)
+    plans = plans_of(sched)
     c = zone_counts(binder, zones)
     assert sum(c.values()) == 3 and len(c) == 1, c
     assert set(node_counts(binder).values()) == {1}
@@ -368,7 +349,7 @@ def test_subgroup_policy_jobs_stay_cycle_granular():
         p.affinity = {"podAffinity": {"group": "web",
                                       "topologyKey": "zone"}}
         store.create("Pod", p)
-    plans = _plans_of(sched)
+    plans = plans_of(sched)
     assert plans and plans[0].classes
     assert all(cp.affinity is None for cp in plans[0].classes)
     assert plans[0].spread_groups == []
@@ -385,7 +366,7 @@ def test_exact_class_loses_the_session_open_bit():
     sched.run_once()
     job(store, "web-a", 2, 1)
     job(store, "web-b", 2, 1)              # same signature: would bundle
-    plan = _plans_of(sched)[0]
+    plan = plans_of(sched)[0]
     assert len(plan.classes) == 2 and len(plan.spread_groups) == 1
     assert plan.spread_groups[0].count.tolist() == [1, 0, 0]
     for cp in plan.classes:

@@ -6,6 +6,7 @@ from collections import Counter
 
 import pytest
 
+from _plan_spy import plans_of
 from volcano_amd.scheduler import (FakeBinder, Scheduler, SchedulerCache,
                                    default_config)
 from volcano_amd.scheduler.config import PluginOption, Tier
@@ -192,26 +193,6 @@ def test_one_pod_per_cycle_alternates(exact):
     assert placed.count("z1") == 2 and placed.count("z2") == 2
 
 
-def _plans_of(sched):
-    """Run one cycle, returning the plans the torch runner was given."""
-    from volcano_amd.scheduler import plan as planmod
-    import volcano_amd.scheduler.actions.allocate as alloc
-    seen = []
-    real = planmod.run_plan_torch
-
-    def spy(plan):
-        seen.append(plan)
-        return real(plan)
-
-    orig = alloc.run_plan_torch
-    alloc.run_plan_torch = spy
-    try:
-        sched.run_once()
-    finally:
-        alloc.run_plan_torch = orig
-    return seen
-
-
 def test_subgroup_policy_jobs_stay_cycle_granular():
     """Out of scope by design: a SubGroupPolicy job can lose placements
     after the select has counted them, so ``exact`` is ignored for it."""
@@ -227,7 +208,7 @@ def test_subgroup_policy_jobs_stay_cycle_granular():
                                          "topologyKey": "zone",
                                          "maxSkew": 1}}
         store.create("Pod", p)
-    plans = _plans_of(sched)
+    plans = plans_of(sched)
     assert plans and plans[0].classes
     assert all(cp.spread is None for cp in plans[0].classes)
     assert plans[0].spread_groups == []
@@ -255,7 +236,7 @@ def test_soft_shard_coordinator_stays_cycle_granular():
         if action.name == "allocate":
             action.coordinator = Coordinator()
     spread_job(store, "web", 7, 1)
-    plans = _plans_of(sched)
+    plans = plans_of(sched)
     assert plans and all(cp.spread is None for cp in plans[0].classes)
     assert len(binder.binds) == 7
 
@@ -271,7 +252,7 @@ def test_exact_classes_carry_a_spread_descriptor():
     sched.run_once()                       # zone a now saturated at open
     spread_job(store, "web-a", 2, 1)
     spread_job(store, "web-b", 2, 1)       # same signature: would bundle
-    plan = _plans_of(sched)[0]
+    plan = plans_of(sched)[0]
     assert len(plan.classes) == 2 and len(plan.spread_groups) == 1
     g = plan.spread_groups[0]
     assert g.count.tolist() == [1, 0, 0]

@@ -32,7 +32,7 @@ BOUND_S = TaskStatus.BOUND
 from ...ops import host
 from ...ops import reference as ref_ops
 from ...utils.metrics import METRICS
-from ..plan import (BundleEntry, ClassPlan, CyclePlan, JobPlan, run_plan_hip,
+from ..plan import (BundleEntry, ClassPlan, CyclePlan, run_plan_hip,
                     run_plan_torch)
 
 
@@ -73,620 +73,7 @@ class AllocateAction:
         plan = CyclePlan(nt, ssn.queue_limit, ssn.queue_alloc)
         plan.dim_w = ssn.dim_weight_vector()
         plan.bias = getattr(ssn, "score_bias", None)
-        w = ssn.score_weights
-        predicates = getattr(ssn, "predicates", None)
-
-        # -- build the worksheet (buildAllocateContext analog) --------------
-        # Columnar path: selection (phase/pending/valid), queue grouping
-        # and job ordering all run as array ops over the JobTable; the
-        # legacy per-job path remains for unaligned tables (mid-cycle
-        # direct mutations in tests).
-        jt = getattr(ssn, "job_table", None)
-        if jt is not None and len(jt.jobs) != len(ssn.jobs):
-            jt = None
-        # parallel worksheets: jobs_l[i] is the i-th job in plan order,
-        # qi_l[i] its queue index (no per-job tuple boxing)
-        jobs_l: List = []
-        qi_l: List[int] = []
-        # run metadata (parallel to jobs_l, columnar path only): maximal
-        # runs of consecutive atomic same-signature jobs emit as ONE
-        # fused bundle without per-job plan_atom/signature work
-        elig_l = sig_l = gm_l = None
-        if jt is not None:
-            from ..jobtable import PH_INQUEUE, PH_RUNNING
-            mask = ((jt.phase == PH_INQUEUE) | (jt.phase == PH_RUNNING)) \
-                & (jt.npend > 0)
-            vcols = ssn.job_valid_cols
-            if len(vcols) == len(ssn.job_valid_fns):
-                for fn in vcols:
-                    mask &= fn(jt)
-                sel = np.nonzero(mask)[0]
-            else:
-                sel = np.nonzero(mask)[0]
-                if len(sel):
-                    keep = np.fromiter(
-                        (ssn.job_valid(jt.jobs[int(k)]) for k in sel),
-                        dtype=bool, count=len(sel))
-                    sel = sel[keep]
-            if len(sel):
-                qis = jt.qi[sel]
-                qname_by_qi = {i: n for n, i in ssn.queue_index.items()}
-                present = np.unique(qis[qis >= 0])
-                queues = [ssn.queues[qname_by_qi[int(i)]] for i in present
-                          if qname_by_qi.get(int(i)) in ssn.queues]
-                jjobs = jt.jobs
-                track_runs = not ssn.class_bias_fns
-                if track_runs:
-                    elig_l, sig_l, gm_l = [], [], []
-                for q in ssn.sorted_queues(queues):
-                    if not q.is_open or ssn.queue_overused(q):
-                        continue
-                    # Allocatable is queue-scoped (quota gates; the exact
-                    # per-task bound is enforced in-kernel).  CONTRACT:
-                    # allocatable_fns must be job-independent (job=None).
-                    if not ssn.allocatable(q, None):
-                        continue
-                    qi = ssn.queue_index[q.name]
-                    rows = ssn.ordered_job_rows(jt, sel[qis == qi])
-                    # tolist(): native ints, no per-row numpy scalar boxing
-                    rl = rows.tolist()
-                    jobs_l.extend(jjobs[k] for k in rl)
-                    qi_l.extend([qi] * len(rl))
-                    if track_runs:
-                        elig_l.extend(((jt.sigid[rows] >= 0)
-                                       & (jt.npend[rows] == jt.ntasks[rows])
-                                       & ~jt.subpol[rows]).tolist())
-                        sig_l.extend(jt.sigid[rows].tolist())
-                        gm_l.extend(jt.gangmin[rows].tolist())
-        else:
-            by_queue = {}
-            for job in ssn.jobs.values():
-                if job.phase not in (PodGroupPhase.INQUEUE.value,
-                                     PodGroupPhase.RUNNING.value):
-                    continue
-                if not job.task_status_index.get(PENDING_S):
-                    continue      # no list build — emptiness check only
-                if not ssn.job_valid(job):
-                    continue
-                by_queue.setdefault(job.queue, []).append(job)
-
-            queues = [ssn.queues[q] for q in by_queue if q in ssn.queues]
-            for q in ssn.sorted_queues(queues):
-                if not q.is_open or ssn.queue_overused(q):
-                    continue
-                jobs_q = by_queue[q.name]
-                gate = ssn.allocatable(q, None) if jobs_q else True
-                if not gate:
-                    continue
-                qi = ssn.queue_index[q.name]
-                sj = ssn.sorted_jobs(jobs_q)
-                jobs_l.extend(sj)
-                qi_l.extend([qi] * len(sj))
-
-        # Gang bundling: a run of consecutive jobs whose single pending
-        # class has identical (queue, signature) is fused into ONE kernel
-        # pass — ntasks summed, per-job gang minimums enforced at apply
-        # (tail-trim).  This is the dominant shape at scale (many identical
-        # gangs) and collapses 2 launches/job into 2 launches/run.
-        open_bundle: ClassPlan = None
-        open_key = None
-
-        def close_bundle():
-            nonlocal open_bundle, open_key
-            if open_bundle is not None:
-                # in-kernel revert only when even the EASIEST bundled gang
-                # cannot place (the apply walk settles per-job minimums);
-                # min_needed is min-tracked as entries append
-                easiest = open_bundle.min_needed
-                plan.jobs.append(JobPlan(
-                    job_key=open_bundle.job_key,
-                    class_begin=len(plan.classes),
-                    class_end=len(plan.classes) + 1,
-                    occupied=0,
-                    min_available=easiest))
-                plan.classes.append(open_bundle)
-            open_bundle, open_key = None, None
-
-        def bundle_in(cp: ClassPlan, job, qi: int, gang_min: int,
-                      sig: str) -> None:
-            nonlocal open_bundle, open_key
-            key = (qi, sig)
-            tasks = cp.tclass.tasks        # already a fresh per-job list
-            if open_bundle is not None and key == open_key:
-                b = open_bundle
-                b.bundle.append(BundleEntry(job.key, tasks, len(tasks),
-                                            gang_min, job))
-                b.ntasks_override += len(tasks)
-                if gang_min < b.min_needed:
-                    b.min_needed = gang_min
-                return
-            close_bundle()
-            # open the bundle on the ORIGINAL ClassPlan: the instance
-            # count lives in ntasks_override, per-job boundaries in the
-            # bundle list; tclass stays the first job's (its tasks[0] is
-            # the representative for handlers/constraint builders)
-            cp.job_key = job.key
-            cp.min_needed = gang_min
-            cp.ntasks_override = len(tasks)
-            cp.bundle = [BundleEntry(job.key, tasks, len(tasks), gang_min,
-                                     job)]
-            open_bundle, open_key = cp, key
-
-        _MISS = object()
-        req_memo = {}
-        # (sig, qi) → (req, tolerated, require, forbid): one lookup per
-        # job covers both the request vector and the constraint planes
-        cons_memo = {}
-        from ...api.types import TaskStatus as _TS
-        w_least = w.get("least", 1.0)
-        w_most = w.get("most", 0.0)
-        w_bal = w.get("bal", 0.0)
-        bias_fns = ssn.class_bias_fns
-        # the per-job loop of a fused run, in the host extension
-        run_entries = host.load().bundle_entries \
-            if host.native_jobs_enabled() else self._run_entries_py
-
-        def class_bias(tc, job):
-            out = None
-            for fn in bias_fns:
-                b = fn(tc, job)
-                if b is not None:
-                    out = b if out is None else out + b
-            return out
-
-        # exact topology spread (topologyspread plugin, ``exact: true``):
-        # matching classes go through the per-placement spread select.
-        # Not under the soft-shard coordinator, whose conflict reconcile
-        # can drop placements the kernel already counted.
-        spread_exact = getattr(ssn, "spread_exact", None) \
-            if self.coordinator is None else None
-        spread_group_of: Dict[int, int] = {}   # plugin group → plan group
-
-        def spread_attach(cp: ClassPlan, sp) -> None:
-            """Route cp through the spread select; its constraint words
-            lose the session-open saturation bit (the memoized arrays are
-            shared with the cycle-granular consumers — copy first)."""
-            g, skew = sp
-            pg = spread_group_of.get(g)
-            if pg is None:
-                pg = spread_group_of[g] = plan.add_spread_group(
-                    spread_exact.dom_of[g], spread_exact.count[g])
-            cp.spread = (pg, skew)
-            bit = spread_exact.sat_bit[g]
-            if bit is not None and bit // 64 < len(cp.forbid):
-                cp.forbid = cp.forbid.copy()
-                cp.forbid[bit // 64] &= ~(np.int64(1) << np.int64(bit % 64))
-
-        # exact inter-pod affinity (interpodaffinity plugin, ``exact:
-        # true``): the same routing for the classes of an affinity or keyed
-        # anti-affinity rule.  One domain rule per class — spread wins.
-        affinity_exact = getattr(ssn, "affinity_exact", None) \
-            if self.coordinator is None else None
-        affinity_group_of: Dict[int, int] = {}   # plugin rule → plan group
-
-        def affinity_attach(cp: ClassPlan, af) -> None:
-            """Route cp through the domain mask; its constraint words lose
-            the rule's session-open bit (hosting set / occupied domains) —
-            copy first, the memoized arrays are shared."""
-            g, mode = af
-            pg = affinity_group_of.get(g)
-            if pg is None:
-                pg = affinity_group_of[g] = plan.add_spread_group(
-                    affinity_exact.dom_of[g], affinity_exact.count[g])
-            cp.affinity = (pg, mode)
-            bit = affinity_exact.open_bit[g]
-            if bit is not None:
-                if mode == 1 and bit // 64 < len(cp.require):
-                    cp.require = cp.require.copy()
-                    cp.require[bit // 64] &= \
-                        ~(np.int64(1) << np.int64(bit % 64))
-                elif mode == 2 and bit // 64 < len(cp.forbid):
-                    cp.forbid = cp.forbid.copy()
-                    cp.forbid[bit // 64] &= \
-                        ~(np.int64(1) << np.int64(bit % 64))
-
-        # exact network topology (network-topology-aware plugin, ``exact:
-        # true``): a job that plans as ONE single-class gang, and every
-        # SubGroupPolicy subgroup with a topology override, has its
-        # hypernode chosen on the device from the live per-node capacity.
-        # Not under the soft-shard coordinator, as for spread.
-        hypernode_exact = getattr(ssn, "hypernode_exact", None) \
-            if self.coordinator is None else None
-        hypernode_row: List[int] = []            # the plan's one leaf row
-
-        def hypernode_attach(cp: ClassPlan, job, hn, need: int) -> None:
-            """Route cp through the hypernode mask.  The caller built its
-            constraint words with ``skip_topology``: the host scan over the
-            domains never ran and no ``hn:`` (or nowhere) bit is set."""
-            tiers, pin, soft = hn
-            if not hypernode_row:
-                hypernode_row.append(plan.add_hypernode_row(
-                    hypernode_exact.leaf_of, hypernode_exact.n_leaves))
-            cp.hypernode = plan.add_hypernode_group(
-                hypernode_row[0], ref_ops.hypernode_table(
-                    tiers, max(1, int(need)), hypernode_exact.n_leaves,
-                    pin, soft))
-
-        # exact device share (deviceshare plugin, ``exact: true``): a class
-        # with a device request is packed per card on the device, per
-        # placement.  Not under the soft-shard coordinator, which keeps the
-        # host bit.
-        device_exact = getattr(ssn, "device_exact", None) \
-            if self.coordinator is None else None
-
-        def device_attach(cp: ClassPlan) -> None:
-            """Attach cp's device request, if it has one; its constraint
-            words lose the session-open ``dev-unfit:`` bit (copy first, the
-            memoized arrays are shared)."""
-            if device_exact is None:
-                return
-            rq = device_exact.request_of(cp.tclass.tasks[0])
-            if rq is None:
-                return
-            if plan.device_state is None:
-                plan.set_device_state(*device_exact.planes)
-            plan.add_device_request(cp, *rq.signature())
-            bit = device_exact.unfit_bits.get(rq.signature())
-            if bit is not None and bit // 64 < len(cp.forbid):
-                cp.forbid = cp.forbid.copy()
-                cp.forbid[bit // 64] &= ~(np.int64(1) << np.int64(bit % 64))
-
-        def device_job(jb) -> bool:
-            t0_ = next(iter(jb.task_status_index.get(
-                _TS.PENDING, {}).values()), None)
-            return t0_ is not None and \
-                device_exact.request_of(t0_) is not None
-
-        # such jobs never join a fused signature run
-        if device_exact is not None and elig_l is not None:
-            for ix, jb in enumerate(jobs_l):
-                if elig_l[ix] and device_job(jb):
-                    elig_l[ix] = False
-
-        # exact NUMA pinning (numaaware plugin, ``exact: true``): a class
-        # with a topology policy is pinned per zone on the device, per
-        # placement.  Not under the soft-shard coordinator, which keeps the
-        # host bit and the host choice.
-        numa_exact = getattr(ssn, "numa_exact", None) \
-            if self.coordinator is None else None
-
-        def numa_attach(cp: ClassPlan) -> None:
-            """Attach cp's NUMA request, if it has one; its constraint words
-            lose the session-open ``numa-unfit:`` bit (copy first, the
-            memoized arrays are shared)."""
-            if numa_exact is None:
-                return
-            rq = numa_exact.request_of(cp.tclass.tasks[0])
-            if rq is None:
-                return
-            if plan.numa_state is None:
-                plan.set_numa_state(numa_exact.plane)
-            plan.add_numa_request(cp, *rq)
-            bit = numa_exact.unfit_bits.get(cp.tclass.request.get(_CPU))
-            if bit is not None and bit // 64 < len(cp.forbid):
-                cp.forbid = cp.forbid.copy()
-                cp.forbid[bit // 64] &= ~(np.int64(1) << np.int64(bit % 64))
-
-        # such jobs never join a fused signature run
-        if numa_exact is not None and elig_l is not None:
-            for ix, jb in enumerate(jobs_l):
-                t0_ = next(iter(jb.task_status_index.get(
-                    _TS.PENDING, {}).values()), None) if elig_l[ix] else None
-                if t0_ is not None and \
-                        numa_exact.request_of(t0_) is not None:
-                    elig_l[ix] = False
-
-        if hypernode_exact is not None and elig_l is not None:
-            # each such job needs its own domain: none joins a fused run
-            for ix, jb in enumerate(jobs_l):
-                if elig_l[ix] and \
-                        hypernode_exact.resolve_job(jb) is not None:
-                    elig_l[ix] = False
-
-        # such jobs never join a fused signature run
-        if (spread_exact is not None or affinity_exact is not None) \
-                and elig_l is not None:
-            for ix, jb in enumerate(jobs_l):
-                if elig_l[ix]:
-                    t0_ = next(iter(jb.task_status_index.get(
-                        _TS.PENDING, {}).values()), None)
-                    if t0_ is None:
-                        continue
-                    if (spread_exact is not None and
-                            spread_exact.resolve_task(t0_) is not None) or \
-                            (affinity_exact is not None and
-                             affinity_exact.resolve_task(t0_) is not None):
-                        elig_l[ix] = False
-
-        # nominated gangs take the host fast path — exclude them from runs
-        if elig_l is not None and self.coordinator is None and \
-                getattr(ssn.cache, "had_nominations", False):
-            for ix, jb in enumerate(jobs_l):
-                if jb._nom:
-                    elig_l[ix] = False
-
-        L = len(jobs_l)
-        skip_until = -1
-        for i in range(L):
-            if i < skip_until:
-                continue
-            job = jobs_l[i]
-            qi = qi_l[i]
-
-            # -- fused run: consecutive atomic jobs with one interned
-            # signature in one queue emit as a single bundled ClassPlan —
-            # no per-job signature/constraint work (the dominant shape
-            # after signature-grouped ordering)
-            if elig_l is not None and elig_l[i]:
-                s = sig_l[i]
-                j = i + 1
-                while j < L and elig_l[j] and sig_l[j] == s \
-                        and qi_l[j] == qi:
-                    j += 1
-                if j > i + 1:
-                    skip_until = j
-                    atom = job.plan_atom()
-                    sig, role, request, priority = atom
-                    rep0 = next(iter(job.task_status_index.get(
-                        _TS.PENDING).values()))
-                    if rep0.best_effort:
-                        continue  # BestEffort is backfill's (allocate.go:265)
-                    ckey = (sig, qi)
-                    got = cons_memo.get(ckey, _MISS)
-                    if got is _MISS:
-                        req = nt.req_vector(
-                            next(iter(job.task_status_index.get(
-                                _TS.PENDING).values())))
-                        if req is None:
-                            got = None
-                        else:
-                            tc0 = TaskClass(
-                                signature=sig, role=role, request=request,
-                                tasks=[next(iter(job.task_status_index.get(
-                                    _TS.PENDING).values()))],
-                                priority=priority)
-                            if predicates is not None:
-                                tol, require, forbid = \
-                                    predicates.class_constraints(tc0, job)
-                            else:
-                                tol = -1
-                                W = max(nt.labels.words, 1)
-                                require = np.zeros(W, dtype=np.int64)
-                                forbid = np.zeros(W, dtype=np.int64)
-                            got = (req, tol, require, forbid)
-                        cons_memo[ckey] = got
-                    if got is None:
-                        continue  # asks for a resource no node offers
-                    req, tol, require, forbid = got
-                    entries, total, mn = run_entries(
-                        jobs_l, i, j, gm_l, PENDING_S, BundleEntry)
-                    if not entries:
-                        continue
-                    close_bundle()
-                    e0 = entries[0]
-                    tc = TaskClass(signature=sig, role=role,
-                                   request=request, tasks=e0.tasks,
-                                   priority=priority)
-                    cp = ClassPlan(tclass=tc, job_key=e0.job_key,
-                                   queue_idx=qi, req=req, tolerated=tol,
-                                   require=require, forbid=forbid,
-                                   min_needed=mn, w_least=w_least,
-                                   w_most=w_most, w_bal=w_bal)
-                    cp.ntasks_override = total
-                    cp.bundle = entries
-                    plan.jobs.append(JobPlan(
-                        job_key=e0.job_key,
-                        class_begin=len(plan.classes),
-                        class_end=len(plan.classes) + 1,
-                        occupied=0, min_available=mn))
-                    plan.classes.append(cp)
-                    continue
-                # singleton run: fall through to the per-job path (it
-                # may open/continue a bundle with neighbours)
-
-            # -- SubGroupPolicy (reference types.go:218 SubGroupPolicySpec
-            # + allocate.go allocateForSubJob): matching pods partition
-            # into gang-atomic subgroups of subGroupSize, each planned as
-            # its own single-class gang (in-kernel revert); the job-level
-            # minSubGroups gate is applied after the run (_apply gating).
-            if job.podgroup is not None and \
-                    job.podgroup.spec.sub_group_policy:
-                close_bundle()
-                self._plan_subgroups(ssn, plan, job, qi, predicates,
-                                     w_least, w_most, w_bal,
-                                     hypernode_exact, hypernode_attach)
-                continue
-
-            # -- nomination fast path (reference allocate.go:797
-            # NominatedNodeName): a gang pipelined by last cycle's preempt
-            # re-checks fit on its nominated nodes and commits host-side,
-            # skipping scoring entirely.  Disabled under soft-sharding
-            # (commits must flow through the conflict reconcile).
-            if self.coordinator is None and job._nom and \
-                    self._try_nominated(ssn, job, qi, predicates):
-                continue
-
-            # -- steady-state fast path: the whole job is one pending class
-            atom = job.plan_atom()
-            pend = job.task_status_index.get(_TS.PENDING, {})
-            if atom and pend and len(pend) == len(job.tasks):
-                sig, role, request, priority = atom
-                first = next(iter(pend.values()))
-                if first.gated or first.best_effort:
-                    continue    # BestEffort is backfill's (allocate.go:265)
-                # bundle continuation: identical (queue, signature) run —
-                # append the gang entry directly, skipping the
-                # TaskClass/ClassPlan/constraint work bundle_in would
-                # discard anyway (dominant shape: thousands of identical
-                # gangs back to back)
-                sp = spread_exact.resolve_task(first) \
-                    if spread_exact is not None else None
-                af = affinity_exact.resolve_task(first) \
-                    if affinity_exact is not None and sp is None else None
-                hn = hypernode_exact.resolve_job(job) \
-                    if hypernode_exact is not None and sp is None \
-                    and af is None else None
-                dv = device_exact.request_of(first) \
-                    if device_exact is not None else None
-                nu = numa_exact.request_of(first) \
-                    if numa_exact is not None else None
-                if sp is None and af is None and hn is None \
-                        and dv is None and nu is None and not bias_fns \
-                        and open_bundle is not None \
-                        and open_key == (qi, sig):
-                    tasks = list(pend.values())
-                    mtm = job._mtm
-                    if mtm is None:
-                        mtm = job.min_task_member
-                    gang_min = job.min_available if not mtm else \
-                        max(job.min_available, mtm.get(role, 0))
-                    b = open_bundle
-                    b.bundle.append(
-                        BundleEntry(job.key, tasks, len(tasks), gang_min,
-                                    job))
-                    b.ntasks_override += len(tasks)
-                    if gang_min < b.min_needed:
-                        b.min_needed = gang_min
-                    continue
-                # a hypernode job's words are built without the topology
-                # hook (no host scan over the domains), so they are not
-                # the memoized ones
-                ckey = (sig, qi)
-                got = cons_memo.get(ckey, _MISS) if hn is None else _MISS
-                if got is _MISS:
-                    req = nt.req_vector(first)
-                    if req is None:
-                        got = None
-                    else:
-                        tc0 = TaskClass(signature=sig, role=role,
-                                        request=request, tasks=[first],
-                                        priority=priority)
-                        if predicates is not None:
-                            tol, require, forbid = \
-                                predicates.class_constraints(
-                                    tc0, job, skip_topology=hn is not None)
-                        else:
-                            tol = -1
-                            W = max(nt.labels.words, 1)
-                            require = np.zeros(W, dtype=np.int64)
-                            forbid = np.zeros(W, dtype=np.int64)
-                        got = (req, tol, require, forbid)
-                    if hn is None:
-                        cons_memo[ckey] = got
-                if got is None:
-                    continue      # asks for a resource no node offers
-                req, tol, require, forbid = got
-                tc = TaskClass(signature=sig, role=role, request=request,
-                               tasks=list(pend.values()), priority=priority)
-                mtm = job._mtm
-                if mtm is None:
-                    mtm = job.min_task_member
-                gang_min = job.min_available if not mtm else \
-                    max(job.min_available, mtm.get(role, 0))
-                cp = ClassPlan(tclass=tc, job_key=job.key, queue_idx=qi,
-                               req=req, tolerated=tol, require=require,
-                               forbid=forbid, min_needed=gang_min,
-                               w_least=w_least, w_most=w_most, w_bal=w_bal)
-                if bias_fns:
-                    cp.bias = class_bias(tc, job)
-                if sp is not None:
-                    spread_attach(cp, sp)
-                elif af is not None:
-                    affinity_attach(cp, af)
-                elif hn is not None:
-                    hypernode_attach(cp, job, hn, gang_min)
-                if dv is not None:
-                    device_attach(cp)
-                if nu is not None:
-                    numa_attach(cp)
-                # biased, domain-rule, device and NUMA classes never fuse
-                if cp.bias is not None or cp.spread is not None \
-                        or cp.affinity is not None \
-                        or cp.hypernode is not None \
-                        or cp.device is not None or cp.numa is not None:
-                    close_bundle()
-                    plan.add_job(job, [cp])
-                else:
-                    bundle_in(cp, job, qi, gang_min, sig)
-                continue
-
-            classes: List[ClassPlan] = []
-            skipped = False
-            pending = [tc for tc in job.pending_classes()
-                       if not tc.tasks[0].best_effort]
-            # BestEffort is backfill's (allocate.go:265).  A job whose
-            # pending tasks form ONE class may have its hypernode chosen on
-            # the device: resolved before the constraints are built, so
-            # that the topology hook's host scan never runs for it
-            hn = None
-            if hypernode_exact is not None and len(pending) == 1 and not (
-                    (spread_exact is not None and spread_exact.resolve_task(
-                        pending[0].tasks[0]) is not None) or
-                    (affinity_exact is not None and
-                     affinity_exact.resolve_task(
-                         pending[0].tasks[0]) is not None)):
-                hn = hypernode_exact.resolve_job(job)
-            for tc in pending:
-                req = nt.req_vector(tc.tasks[0])
-                if req is None:
-                    skipped = True    # asks for a resource no node offers
-                    continue
-                if predicates is not None:
-                    tol, require, forbid = predicates.class_constraints(
-                        tc, job, skip_topology=hn is not None)
-                else:
-                    tol = -1          # tolerate everything
-                    W = max(nt.labels.words, 1)
-                    require = np.zeros(W, dtype=np.int64)
-                    forbid = np.zeros(W, dtype=np.int64)
-                need = job.min_task_member.get(tc.role, 0)
-                min_needed = max(0, need - job.role_occupied(tc.role))
-                cp = ClassPlan(
-                    tclass=tc, job_key=job.key, queue_idx=qi, req=req,
-                    tolerated=tol, require=require, forbid=forbid,
-                    min_needed=min_needed, w_least=w.get("least", 1.0),
-                    w_most=w.get("most", 0.0), w_bal=w.get("bal", 0.0))
-                if bias_fns:
-                    cp.bias = class_bias(tc, job)
-                sp = spread_exact.resolve_task(tc.tasks[0]) \
-                    if spread_exact is not None else None
-                if sp is not None:
-                    spread_attach(cp, sp)
-                elif affinity_exact is not None:
-                    af = affinity_exact.resolve_task(tc.tasks[0])
-                    if af is not None:
-                        affinity_attach(cp, af)
-                device_attach(cp)
-                numa_attach(cp)
-                classes.append(cp)
-            if skipped and classes and job.min_available > sum(
-                    c.tclass.count for c in classes) + job.occupied_count:
-                # gang can never be satisfied this cycle
-                continue
-            if not classes:
-                continue
-            if hn is not None:
-                hypernode_attach(
-                    classes[0], job, hn,
-                    max(job.min_available - job.occupied_count,
-                        classes[0].min_needed))
-
-            bundleable = (len(classes) == 1 and job.occupied_count == 0
-                          and classes[0].tclass.count == len(job.tasks)
-                          and classes[0].bias is None
-                          and classes[0].spread is None
-                          and classes[0].affinity is None
-                          and classes[0].hypernode is None
-                          and classes[0].device is None
-                          and classes[0].numa is None)
-            if bundleable:
-                cp = classes[0]
-                gang_min = max(job.min_available, cp.min_needed)
-                bundle_in(cp, job, qi, gang_min, cp.tclass.signature)
-            else:
-                close_bundle()
-                plan.add_job(job, classes)
-        close_bundle()
+        rules = _PlanBuilder(self, ssn, plan).build()
 
         if plan.n_classes == 0 and self.coordinator is None:
             return
@@ -702,7 +89,7 @@ class AllocateAction:
         bad = frozenset()
         if coord is not None:
             bad = coord.find_conflicts(nt, used_before)
-        if result is not None and device_exact is not None:
+        if result is not None and rules.device is not None:
             # The cards the cycle chose, for the plugin's on_allocate, keyed
             # by the class object the event carries.  Two invariants make
             # the hand-off line up: (1) a device class never bundles, so the
@@ -710,14 +97,14 @@ class AllocateAction:
             # its pieces; (2) the walk and class_cards both skip exactly
             # the log entries with count <= 0 and keep log order, so the
             # i-th card list belongs to the i-th task of the event.
-            device_exact.cards = {
+            rules.device.cards = {
                 id(cp.tclass): result.class_cards(c)
                 for c, cp in enumerate(plan.classes)
                 if cp.device is not None}
-        if result is not None and numa_exact is not None:
+        if result is not None and rules.numa is not None:
             # the zones the cycle chose, handed over the same way and by
             # the same two invariants (a NUMA class never bundles either)
-            numa_exact.zones = {
+            rules.numa.zones = {
                 id(cp.tclass): result.class_zones(c)
                 for c, cp in enumerate(plan.classes)
                 if cp.numa is not None}
@@ -730,94 +117,6 @@ class AllocateAction:
         METRICS.observe("allocate:plan_build", t1 - t0)
         METRICS.observe("allocate:plan_run", t2 - t1)
         METRICS.observe("allocate:apply", t3 - t2)
-
-    def _plan_subgroups(self, ssn, plan, job, qi: int, predicates,
-                        w_least, w_most, w_bal, hypernode_exact=None,
-                        hypernode_attach=None) -> None:
-        """Partition the job's pending pods per SubGroupPolicy entry and
-        emit one single-class gang JobPlan per complete subgroup.  Pods
-        left unmatched (or in an incomplete tail chunk) stay pending
-        this cycle.  Synthetic job keys alias back to the real job for
-        the apply walk; the minSubGroups family gate lives in plan
-        metadata and is enforced post-run.
-
-        Semantics notes (reference types.go:224: SubGroupPolicy is the
-        evolution of minTaskMember): when present it supersedes the
-        job-level minMember for admission-to-placement — minSubGroups is
-        the job gate; corrective actions (preempt/reclaim) treat the job
-        conventionally through its pending tasks."""
-        from ...api.types import TaskStatus as _TS
-        pend = [t for t in job.task_status_index.get(
-            _TS.PENDING, {}).values() if not t.gated]
-        claimed = set()
-        if not hasattr(plan, "job_alias"):
-            plan.job_alias = {}
-            plan.subgroup_families = []
-        for pi, pol in enumerate(job.podgroup.spec.sub_group_policy):
-            size = max(1, int(pol.get("subGroupSize", 1)))
-            min_subs = int(pol.get("minSubGroups", 0))
-            sel = pol.get("labelSelector") or {}
-            keys = pol.get("matchLabelKeys") or []
-            topo = pol.get("networkTopology")
-            matched = []
-            for t in pend:
-                if id(t) in claimed or t.pod is None:
-                    continue
-                lbl = t.pod.meta.labels
-                if all(lbl.get(k) == v for k, v in sel.items()):
-                    matched.append(t)
-            groups: Dict[tuple, List] = {}
-            for t in matched:
-                gk = tuple(t.pod.meta.labels.get(k) for k in keys)
-                groups.setdefault(gk, []).append(t)
-            members = []
-            sg = 0
-            for gk in sorted(groups, key=lambda g: tuple(map(str, g))):
-                ts = groups[gk]
-                for off in range(0, len(ts) - size + 1, size):
-                    chunk = ts[off:off + size]
-                    for t in chunk:
-                        claimed.add(id(t))
-                    first = chunk[0]
-                    req = ssn.node_tensors.req_vector(first)
-                    if req is None:
-                        continue
-                    tc = TaskClass(signature=first.class_signature(),
-                                   role=first.role, request=first.request,
-                                   tasks=chunk, priority=first.priority,
-                                   topology=topo)
-                    # exact network topology: the subgroup's domain is
-                    # chosen on the device — the host hook (and its
-                    # reservation ledger) is not consulted
-                    hn = hypernode_exact.resolve_spec(topo) \
-                        if hypernode_exact is not None and topo else None
-                    if predicates is not None:
-                        tol, require, forbid = \
-                            predicates.class_constraints(
-                                tc, job, skip_topology=hn is not None)
-                    else:
-                        W = max(ssn.node_tensors.labels.words, 1)
-                        tol = -1
-                        require = np.zeros(W, dtype=np.int64)
-                        forbid = np.zeros(W, dtype=np.int64)
-                    skey = f"{job.key}#sg{pi}:{sg}"
-                    sg += 1
-                    cp = ClassPlan(tclass=tc, job_key=skey, queue_idx=qi,
-                                   req=req, tolerated=tol, require=require,
-                                   forbid=forbid, min_needed=size,
-                                   w_least=w_least, w_most=w_most,
-                                   w_bal=w_bal)
-                    if hn is not None:
-                        hypernode_attach(cp, job, hn, size)
-                    plan.jobs.append(JobPlan(
-                        job_key=skey, class_begin=len(plan.classes),
-                        class_end=len(plan.classes) + 1, occupied=0,
-                        min_available=size))
-                    plan.classes.append(cp)
-                    plan.job_alias[skey] = job.key
-                    members.append(skey)
-            if members:
-                plan.subgroup_families.append((job.key, min_subs, members))
 
     def _gate_subgroup_families(self, plan, result) -> None:
         """minSubGroups: if fewer than the required number of a policy's
@@ -854,9 +153,8 @@ class AllocateAction:
         still fit (capacity + ready + taints + label planes re-checked on
         the packed mirrors).  Any miss clears the nominations and returns
         False — the job takes the normal scored path."""
-        from ...api.types import TaskStatus as _TS
         job._nom = False      # hint is single-shot per cycle
-        pend_idx = job.task_status_index.get(_TS.PENDING)
+        pend_idx = job.task_status_index.get(PENDING_S)
         if not pend_idx:
             return False
         if not next(iter(pend_idx.values())).nominated_node:
@@ -1259,3 +557,568 @@ class AllocateAction:
         nt.used_t.index_add_(1, idx, -req.unsqueeze(1) * cvec.unsqueeze(0))
         total = sum(c for _, c in pieces)
         plan.queue_alloc[cp.queue_idx] -= float(total) * torch.from_numpy(cp.req)
+
+
+# -- the plan build (buildAllocateContext analog) -------------------------------
+
+_MISS = object()
+_NO_RULES = (None, None, None)      # what ExactRules.resolve mostly answers
+
+
+def _append_entry(b: ClassPlan, job, tasks, gang_min: int) -> None:
+    """One more gang at the end of the bundle class ``b``; its min_needed
+    tracks the EASIEST entry."""
+    b.bundle.append(BundleEntry(job.key, tasks, len(tasks), gang_min, job))
+    b.ntasks_override += len(tasks)
+    if gang_min < b.min_needed:
+        b.min_needed = gang_min
+
+
+def _clear_bit(cp: ClassPlan, words: str, bit) -> None:
+    """Take a session-open bit off cp's ``require`` or ``forbid`` words: the
+    rule it stands for is enforced per placement instead.  The memoized
+    arrays are shared with the cycle-granular consumers — copy first."""
+    if bit is None:
+        return
+    w = getattr(cp, words)
+    if bit // 64 < len(w):
+        w = w.copy()
+        w[bit // 64] &= ~(np.int64(1) << np.int64(bit % 64))
+        setattr(cp, words, w)
+
+
+class _ExactRules:
+    """What the plugins with ``exact: true`` published for this cycle:
+    topology spread, inter-pod affinity, network topology (hypernode),
+    device share and NUMA pinning.  A class that one of them claims is
+    placed by a per-placement path of the cycle runner, loses the rule's
+    session-open constraint bit, and never joins a bundle.  None of them
+    applies under the soft-shard coordinator, whose conflict reconcile can
+    drop placements the kernel already counted."""
+
+    def __init__(self, ssn, plan: CyclePlan, enabled: bool):
+        self.plan = plan
+        self.spread, self.affinity, self.hypernode, self.device, self.numa = [
+            getattr(ssn, f"{name}_exact", None) if enabled else None
+            for name in ("spread", "affinity", "hypernode", "device", "numa")]
+        self.any = any(x is not None for x in (
+            self.spread, self.affinity, self.hypernode, self.device,
+            self.numa))
+        self._group_of: Dict[tuple, int] = {}   # (rule, plugin group) → plan
+        self._leaf_row = None                   # the plan's one leaf row
+
+    def resolve(self, job, task, one_class: bool = True):
+        """(domain rule, device request, NUMA request) of the class whose
+        first pending task is ``task``, or ``_NO_RULES``.  One domain rule
+        per class: spread, else affinity, else hypernode — and the hypernode
+        is a question for a job that plans as ONE class only."""
+        dom = None
+        if self.spread is not None:
+            r = self.spread.resolve_task(task)
+            if r is not None:
+                dom = ("spread", r)
+        if dom is None and self.affinity is not None:
+            r = self.affinity.resolve_task(task)
+            if r is not None:
+                dom = ("affinity", r)
+        if dom is None and one_class and self.hypernode is not None:
+            r = self.hypernode.resolve_job(job)
+            if r is not None:
+                dom = ("hypernode", r)
+        dv = self.device.request_of(task) if self.device is not None else None
+        nu = self.numa.request_of(task) if self.numa is not None else None
+        if dom is None and dv is None and nu is None:
+            return _NO_RULES
+        return dom, dv, nu
+
+    def resolve_subgroup(self, topo):
+        """A SubGroupPolicy subgroup has its hypernode chosen on the device
+        when it carries a topology override; the other rules stay
+        cycle-granular for it (the family gate can drop placements the
+        kernel already counted)."""
+        r = self.hypernode.resolve_spec(topo) \
+            if self.hypernode is not None and topo else None
+        return _NO_RULES if r is None else (("hypernode", r), None, None)
+
+    def attach(self, cp: ClassPlan, rules, need: int) -> None:
+        """Route cp through what ``resolve`` answered.  ``need`` is the
+        gang's open minimum (the hypernode table is built for it).  The
+        words of a hypernode class were built with ``skip_topology``: no
+        ``hn:`` bit is set, so there is none to clear."""
+        dom, dv, nu = rules
+        plan = self.plan
+        if dom is not None and dom[0] == "hypernode":
+            tiers, pin, soft = dom[1]
+            hx = self.hypernode
+            if self._leaf_row is None:
+                self._leaf_row = plan.add_hypernode_row(hx.leaf_of,
+                                                        hx.n_leaves)
+            cp.hypernode = plan.add_hypernode_group(
+                self._leaf_row, ref_ops.hypernode_table(
+                    tiers, max(1, int(need)), hx.n_leaves, pin, soft))
+        elif dom is not None:
+            kind, (g, arg) = dom      # arg: maxSkew (spread), mode (affinity)
+            pub = self.spread if kind == "spread" else self.affinity
+            pg = self._group_of.get((kind, g))
+            if pg is None:
+                pg = self._group_of[kind, g] = plan.add_spread_group(
+                    pub.dom_of[g], pub.count[g])
+            if kind == "spread":
+                cp.spread = (pg, arg)
+                _clear_bit(cp, "forbid", pub.sat_bit[g])    # saturated zones
+            else:
+                cp.affinity = (pg, arg)     # hosting set / occupied domains
+                _clear_bit(cp, "require" if arg == ref_ops.AFFINITY
+                           else "forbid", pub.open_bit[g])
+        if dv is not None:
+            if plan.device_state is None:
+                plan.set_device_state(*self.device.planes)
+            plan.add_device_request(cp, *dv.signature())
+            _clear_bit(cp, "forbid",                        # dev-unfit:
+                       self.device.unfit_bits.get(dv.signature()))
+        if nu is not None:
+            if plan.numa_state is None:
+                plan.set_numa_state(self.numa.plane)
+            plan.add_numa_request(cp, *nu)
+            _clear_bit(cp, "forbid", self.numa.unfit_bits.get(  # numa-unfit:
+                cp.tclass.request.get(_CPU)))
+
+
+class _PlanBuilder:
+    """The per-cycle state of the plan build: queues ordered by the
+    queue-order tier, jobs by the job-order tier, one ClassPlan per batch of
+    identical pending tasks.
+
+    Gang bundling: a run of consecutive jobs whose single pending class has
+    identical (queue, signature) is fused into ONE kernel pass — ntasks
+    summed, per-job gang minimums enforced at apply (tail-trim).  This is
+    the dominant shape at scale (many identical gangs) and collapses 2
+    launches/job into 2 launches/run."""
+
+    def __init__(self, action: AllocateAction, ssn, plan: CyclePlan):
+        self.action = action
+        self.ssn = ssn
+        self.plan = plan
+        self.nt = plan.nt
+        self.predicates = getattr(ssn, "predicates", None)
+        w = ssn.score_weights
+        # (w_least, w_most, w_bal): the tail of every ClassPlan(...) below,
+        # whose positional head is (tclass, job_key, queue_idx, req,
+        # tolerated, require, forbid, min_needed)
+        self.weights = (w.get("least", 1.0), w.get("most", 0.0),
+                        w.get("bal", 0.0))
+        self.bias_fns = ssn.class_bias_fns
+        self.rules = _ExactRules(ssn, plan, action.coordinator is None)
+        self.open: ClassPlan = None     # the open bundle and its
+        self.open_key = None            # (queue, signature)
+        # (sig, qi) → (req, tolerated, require, forbid): one lookup per
+        # job covers both the request vector and the constraint planes
+        self.cons_memo = {}
+        # parallel worksheets: jobs_l[i] is the i-th job in plan order,
+        # qi_l[i] its queue index (no per-job tuple boxing)
+        self.jobs_l: List = []
+        self.qi_l: List[int] = []
+        # run metadata (parallel to jobs_l, columnar path only): maximal
+        # runs of consecutive atomic same-signature jobs emit as ONE
+        # fused bundle without per-job plan_atom/signature work
+        self.elig_l = self.sig_l = self.gm_l = None
+
+    def build(self) -> _ExactRules:
+        """Fill the plan; returns the cycle's exact rules (the action hands
+        the chosen cards and zones back through them)."""
+        ssn = self.ssn
+        # Columnar path: selection (phase/pending/valid), queue grouping
+        # and job ordering all run as array ops over the JobTable; the
+        # legacy per-job path remains for unaligned tables (mid-cycle
+        # direct mutations in tests).
+        jt = getattr(ssn, "job_table", None)
+        if jt is not None and len(jt.jobs) == len(ssn.jobs):
+            self.select_columnar(jt)
+        else:
+            self.select_legacy()
+        self.mark_unfusable()
+        jobs_l, qi_l = self.jobs_l, self.qi_l
+        elig_l, sig_l = self.elig_l, self.sig_l
+        try_nominated = self.action._try_nominated \
+            if self.action.coordinator is None else None
+        L = len(jobs_l)
+        skip_until = -1
+        for i in range(L):
+            if i < skip_until:
+                continue
+            job = jobs_l[i]
+            qi = qi_l[i]
+            # -- fused run: consecutive atomic jobs with one interned
+            # signature in one queue emit as a single bundled ClassPlan
+            if elig_l is not None and elig_l[i]:
+                s = sig_l[i]
+                j = i + 1
+                while j < L and elig_l[j] and sig_l[j] == s \
+                        and qi_l[j] == qi:
+                    j += 1
+                if j > i + 1:
+                    skip_until = j
+                    self.fused_run(i, j)
+                    continue
+                # singleton run: fall through to the per-job path (it
+                # may open/continue a bundle with neighbours)
+            if job.podgroup is not None and \
+                    job.podgroup.spec.sub_group_policy:
+                self.close_bundle()
+                self.subgroups(job, qi)
+                continue
+            # -- nomination fast path (reference allocate.go:797
+            # NominatedNodeName): a gang pipelined by last cycle's preempt
+            # re-checks fit on its nominated nodes and commits host-side,
+            # skipping scoring entirely.  Disabled under soft-sharding
+            # (commits must flow through the conflict reconcile).
+            if try_nominated is not None and job._nom and \
+                    try_nominated(ssn, job, qi, self.predicates):
+                continue
+            atom = job.plan_atom()
+            pend = job.task_status_index.get(PENDING_S, {})
+            if atom and pend and len(pend) == len(job.tasks):
+                self.single_class(job, qi, atom, pend)
+            else:
+                self.multi_class(job, qi)
+        self.close_bundle()
+        return self.rules
+
+    # -- select and order jobs ----------------------------------------------------
+    def select_columnar(self, jt) -> None:
+        from ..jobtable import PH_INQUEUE, PH_RUNNING
+        ssn = self.ssn
+        mask = ((jt.phase == PH_INQUEUE) | (jt.phase == PH_RUNNING)) \
+            & (jt.npend > 0)
+        vcols = ssn.job_valid_cols
+        if len(vcols) == len(ssn.job_valid_fns):
+            for fn in vcols:
+                mask &= fn(jt)
+            sel = np.nonzero(mask)[0]
+        else:
+            sel = np.nonzero(mask)[0]
+            if len(sel):
+                keep = np.fromiter(
+                    (ssn.job_valid(jt.jobs[int(k)]) for k in sel),
+                    dtype=bool, count=len(sel))
+                sel = sel[keep]
+        if not len(sel):
+            return
+        qis = jt.qi[sel]
+        qname_by_qi = {i: n for n, i in ssn.queue_index.items()}
+        present = np.unique(qis[qis >= 0])
+        queues = [ssn.queues[qname_by_qi[int(i)]] for i in present
+                  if qname_by_qi.get(int(i)) in ssn.queues]
+        jjobs = jt.jobs
+        # biased classes never fuse: no runs when bias functions exist
+        track_runs = not ssn.class_bias_fns
+        if track_runs:
+            self.elig_l, self.sig_l, self.gm_l = [], [], []
+        for q in ssn.sorted_queues(queues):
+            if not q.is_open or ssn.queue_overused(q):
+                continue
+            # Allocatable is queue-scoped (quota gates; the exact
+            # per-task bound is enforced in-kernel).  CONTRACT:
+            # allocatable_fns must be job-independent (job=None).
+            if not ssn.allocatable(q, None):
+                continue
+            qi = ssn.queue_index[q.name]
+            rows = ssn.ordered_job_rows(jt, sel[qis == qi])
+            # tolist(): native ints, no per-row numpy scalar boxing
+            rl = rows.tolist()
+            self.jobs_l.extend(jjobs[k] for k in rl)
+            self.qi_l.extend([qi] * len(rl))
+            if track_runs:
+                self.elig_l.extend(((jt.sigid[rows] >= 0)
+                                    & (jt.npend[rows] == jt.ntasks[rows])
+                                    & ~jt.subpol[rows]).tolist())
+                self.sig_l.extend(jt.sigid[rows].tolist())
+                self.gm_l.extend(jt.gangmin[rows].tolist())
+
+    def select_legacy(self) -> None:
+        ssn = self.ssn
+        by_queue = {}
+        for job in ssn.jobs.values():
+            if job.phase not in (PodGroupPhase.INQUEUE.value,
+                                 PodGroupPhase.RUNNING.value):
+                continue
+            if not job.task_status_index.get(PENDING_S):
+                continue      # no list build — emptiness check only
+            if not ssn.job_valid(job):
+                continue
+            by_queue.setdefault(job.queue, []).append(job)
+        queues = [ssn.queues[q] for q in by_queue if q in ssn.queues]
+        for q in ssn.sorted_queues(queues):
+            if not q.is_open or ssn.queue_overused(q):
+                continue
+            if not ssn.allocatable(q, None):
+                continue
+            qi = ssn.queue_index[q.name]
+            sj = ssn.sorted_jobs(by_queue[q.name])
+            self.jobs_l.extend(sj)
+            self.qi_l.extend([qi] * len(sj))
+
+    def mark_unfusable(self) -> None:
+        """Jobs that an exact rule claims (each needs a class of its own)
+        and nominated gangs (they take the host fast path) stay out of
+        fused runs."""
+        elig_l, rules = self.elig_l, self.rules
+        nominated = self.action.coordinator is None and \
+            getattr(self.ssn.cache, "had_nominations", False)
+        if elig_l is None or not (rules.any or nominated):
+            return
+        for ix, jb in enumerate(self.jobs_l):
+            if not elig_l[ix]:
+                continue
+            if nominated and jb._nom:
+                elig_l[ix] = False
+            elif rules.any:
+                first = next(iter(jb.task_status_index.get(
+                    PENDING_S, {}).values()), None)
+                if first is not None and \
+                        rules.resolve(jb, first) is not _NO_RULES:
+                    elig_l[ix] = False
+
+    # -- constraint words and class construction --------------------------------------
+    def class_words(self, tc, job, skip_topology: bool = False):
+        """(tolerated, require, forbid) of class tc; without a predicates
+        plugin everything is tolerated and nothing asked."""
+        if self.predicates is not None:
+            return self.predicates.class_constraints(
+                tc, job, skip_topology=skip_topology)
+        W = max(self.nt.labels.words, 1)
+        return -1, np.zeros(W, dtype=np.int64), np.zeros(W, dtype=np.int64)
+
+    def atom_words(self, job, qi: int, atom, first,
+                   skip_topology: bool = False):
+        """(req, tolerated, require, forbid) of a job that is one class,
+        memoized per (signature, queue); None when it asks for a resource no
+        node offers.  A hypernode job's words are built without the topology
+        hook (no host scan over the domains), so they are not the memoized
+        ones."""
+        ckey = (atom[0], qi)
+        got = _MISS if skip_topology else self.cons_memo.get(ckey, _MISS)
+        if got is _MISS:
+            req = self.nt.req_vector(first)
+            got = None
+            if req is not None:
+                sig, role, request, priority = atom
+                tc0 = TaskClass(signature=sig, role=role, request=request,
+                                tasks=[first], priority=priority)
+                got = (req, *self.class_words(tc0, job, skip_topology))
+            if not skip_topology:
+                self.cons_memo[ckey] = got
+        return got
+
+    def class_bias(self, tc, job):
+        out = None
+        for fn in self.bias_fns:
+            b = fn(tc, job)
+            if b is not None:
+                out = b if out is None else out + b
+        return out
+
+    # -- bundles ----------------------------------------------------------------------
+    def close_bundle(self) -> None:
+        if self.open is not None:
+            # in-kernel revert only when even the EASIEST bundled gang
+            # cannot place (the apply walk settles per-job minimums)
+            self.plan.add_gang(self.open)
+        self.open = self.open_key = None
+
+    def bundle_in(self, cp: ClassPlan, job, qi: int, gang_min: int,
+                  sig) -> None:
+        key = (qi, sig)
+        tasks = cp.tclass.tasks        # already a fresh per-job list
+        if self.open is not None and key == self.open_key:
+            _append_entry(self.open, job, tasks, gang_min)
+            return
+        self.close_bundle()
+        # open the bundle on the ORIGINAL ClassPlan: the instance
+        # count lives in ntasks_override, per-job boundaries in the
+        # bundle list; tclass stays the first job's (its tasks[0] is
+        # the representative for handlers/constraint builders)
+        cp.job_key = job.key
+        cp.min_needed = gang_min
+        cp.ntasks_override = len(tasks)
+        cp.bundle = [BundleEntry(job.key, tasks, len(tasks), gang_min, job)]
+        self.open, self.open_key = cp, key
+
+    # -- the emission paths -------------------------------------------------------------
+    def fused_run(self, i: int, j: int) -> None:
+        """Jobs [i, j) as ONE bundled class: no per-job signature or
+        constraint work (the dominant shape after signature-grouped
+        ordering); the per-job loop runs in the host extension."""
+        job, qi = self.jobs_l[i], self.qi_l[i]
+        atom = job.plan_atom()
+        first = next(iter(job.task_status_index.get(PENDING_S).values()))
+        if first.best_effort:
+            return        # BestEffort is backfill's (allocate.go:265)
+        words = self.atom_words(job, qi, atom, first)
+        if words is None:
+            return        # asks for a resource no node offers
+        run_entries = host.load().bundle_entries \
+            if host.native_jobs_enabled() else self.action._run_entries_py
+        entries, total, mn = run_entries(
+            self.jobs_l, i, j, self.gm_l, PENDING_S, BundleEntry)
+        if not entries:
+            return
+        self.close_bundle()
+        sig, role, request, priority = atom
+        tc = TaskClass(signature=sig, role=role, request=request,
+                       tasks=entries[0].tasks, priority=priority)
+        cp = ClassPlan(tc, entries[0].job_key, qi, *words, mn, *self.weights)
+        cp.ntasks_override = total
+        cp.bundle = entries
+        self.plan.add_gang(cp)
+
+    def single_class(self, job, qi: int, atom, pend) -> None:
+        """Steady-state fast path: the whole job is one pending class."""
+        sig, role, request, priority = atom
+        first = next(iter(pend.values()))
+        if first.gated or first.best_effort:
+            return        # BestEffort is backfill's (allocate.go:265)
+        rules = self.rules
+        claimed = rules.resolve(job, first) if rules.any else _NO_RULES
+        tasks = list(pend.values())
+        mtm = job._mtm
+        if mtm is None:
+            mtm = job.min_task_member
+        gang_min = job.min_available if not mtm else \
+            max(job.min_available, mtm.get(role, 0))
+        # bundle continuation: identical (queue, signature) run — append
+        # the gang entry directly, skipping the TaskClass/ClassPlan/
+        # constraint work bundle_in would discard anyway
+        if claimed is _NO_RULES and not self.bias_fns \
+                and self.open is not None and self.open_key == (qi, sig):
+            _append_entry(self.open, job, tasks, gang_min)
+            return
+        hn = claimed is not _NO_RULES and claimed[0] is not None \
+            and claimed[0][0] == "hypernode"
+        words = self.atom_words(job, qi, atom, first, skip_topology=hn)
+        if words is None:
+            return        # asks for a resource no node offers
+        tc = TaskClass(signature=sig, role=role, request=request,
+                       tasks=tasks, priority=priority)
+        cp = ClassPlan(tc, job.key, qi, *words, gang_min, *self.weights)
+        if self.bias_fns:
+            cp.bias = self.class_bias(tc, job)
+        if claimed is _NO_RULES and cp.bias is None:
+            self.bundle_in(cp, job, qi, gang_min, sig)
+        else:       # cp.never_bundles, known without asking
+            if claimed is not _NO_RULES:
+                rules.attach(cp, claimed, gang_min)
+            self.close_bundle()
+            self.plan.add_job(job, [cp])
+
+    def multi_class(self, job, qi: int) -> None:
+        """One class per batch of identical pending tasks.  A job whose
+        pending tasks form ONE class may still have its hypernode chosen on
+        the device: resolved before the constraints are built, so that the
+        topology hook's host scan never runs for it."""
+        rules = self.rules
+        # BestEffort is backfill's (allocate.go:265)
+        pending = [tc for tc in job.pending_classes()
+                   if not tc.tasks[0].best_effort]
+        classes: List[ClassPlan] = []
+        skipped = False
+        for tc in pending:
+            req = self.nt.req_vector(tc.tasks[0])
+            if req is None:
+                skipped = True    # asks for a resource no node offers
+                continue
+            claimed = rules.resolve(job, tc.tasks[0], len(pending) == 1) \
+                if rules.any else _NO_RULES
+            hn = claimed[0] is not None and claimed[0][0] == "hypernode"
+            need = job.min_task_member.get(tc.role, 0)
+            min_needed = max(0, need - job.role_occupied(tc.role))
+            cp = ClassPlan(tc, job.key, qi, req,
+                           *self.class_words(tc, job, hn), min_needed,
+                           *self.weights)
+            if self.bias_fns:
+                cp.bias = self.class_bias(tc, job)
+            if claimed is not _NO_RULES:
+                rules.attach(cp, claimed, max(
+                    job.min_available - job.occupied_count, min_needed))
+            classes.append(cp)
+        if not classes:
+            return
+        if skipped and job.min_available > sum(
+                c.tclass.count for c in classes) + job.occupied_count:
+            return        # gang can never be satisfied this cycle
+        cp = classes[0]
+        if len(classes) == 1 and job.occupied_count == 0 \
+                and cp.tclass.count == len(job.tasks) \
+                and not cp.never_bundles:
+            self.bundle_in(cp, job, qi, max(job.min_available, cp.min_needed),
+                           cp.tclass.signature)
+        else:
+            self.close_bundle()
+            self.plan.add_job(job, classes)
+
+    def subgroups(self, job, qi: int) -> None:
+        """SubGroupPolicy (reference types.go:218 SubGroupPolicySpec +
+        allocate.go allocateForSubJob): partition the job's pending pods per
+        policy entry and emit one single-class gang per complete subgroup
+        (in-kernel revert).  Pods left unmatched (or in an incomplete tail
+        chunk) stay pending this cycle.  Synthetic job keys alias back to
+        the real job for the apply walk; the minSubGroups family gate lives
+        in plan metadata and is enforced post-run (_apply gating).
+
+        Semantics notes (reference types.go:224: SubGroupPolicy is the
+        evolution of minTaskMember): when present it supersedes the
+        job-level minMember for admission-to-placement — minSubGroups is
+        the job gate; corrective actions (preempt/reclaim) treat the job
+        conventionally through its pending tasks."""
+        plan = self.plan
+        pend = [t for t in job.task_status_index.get(
+            PENDING_S, {}).values() if not t.gated]
+        claimed = set()
+        if not hasattr(plan, "job_alias"):
+            plan.job_alias = {}
+            plan.subgroup_families = []
+        for pi, pol in enumerate(job.podgroup.spec.sub_group_policy):
+            size = max(1, int(pol.get("subGroupSize", 1)))
+            sel = pol.get("labelSelector") or {}
+            keys = pol.get("matchLabelKeys") or []
+            groups: Dict[tuple, List] = {}
+            for t in pend:
+                if id(t) in claimed or t.pod is None:
+                    continue
+                lbl = t.pod.meta.labels
+                if all(lbl.get(k) == v for k, v in sel.items()):
+                    groups.setdefault(
+                        tuple(lbl.get(k) for k in keys), []).append(t)
+            members = []
+            for gk in sorted(groups, key=lambda g: tuple(map(str, g))):
+                ts = groups[gk]
+                for off in range(0, len(ts) - size + 1, size):
+                    chunk = ts[off:off + size]
+                    claimed.update(map(id, chunk))
+                    skey = f"{job.key}#sg{pi}:{len(members)}"
+                    if self.subgroup_gang(job, qi, chunk, skey,
+                                          pol.get("networkTopology")):
+                        members.append(skey)
+            if members:
+                plan.subgroup_families.append(
+                    (job.key, int(pol.get("minSubGroups", 0)), members))
+
+    def subgroup_gang(self, job, qi: int, chunk, skey: str, topo) -> bool:
+        """One subgroup as a single-class gang of its own.  With exact
+        network topology its domain is chosen on the device — the host hook
+        (and its reservation ledger) is not consulted."""
+        first = chunk[0]
+        req = self.nt.req_vector(first)
+        if req is None:
+            return False
+        tc = TaskClass(signature=first.class_signature(), role=first.role,
+                       request=first.request, tasks=chunk,
+                       priority=first.priority, topology=topo)
+        claimed = self.rules.resolve_subgroup(topo)
+        words = self.class_words(tc, job, claimed is not _NO_RULES)
+        cp = ClassPlan(tc, skey, qi, req, *words, len(chunk), *self.weights)
+        if claimed is not _NO_RULES:
+            self.rules.attach(cp, claimed, len(chunk))
+        self.plan.add_gang(cp)
+        self.plan.job_alias[skey] = job.key
+        return True

@@ -145,6 +145,14 @@ class ClassPlan:
         return self.ntasks_override if self.ntasks_override is not None \
             else self.tclass.count
 
+    @property
+    def never_bundles(self) -> bool:
+        """Carries a bias row, a domain rule, a device or a NUMA request:
+        the class is placed on its own."""
+        return self.bias is not None or self.spread is not None \
+            or self.affinity is not None or self.hypernode is not None \
+            or self.device is not None or self.numa is not None
+
 
 @dataclass(slots=True)
 class JobPlan:
@@ -374,6 +382,15 @@ class CyclePlan:
         self.jobs.append(JobPlan(
             job_key=job.key, class_begin=begin, class_end=len(self.classes),
             occupied=job.occupied_count, min_available=job.min_available))
+
+    def add_gang(self, cp: ClassPlan) -> None:
+        """Append cp as a single-class gang of its own (a bundle, a fused
+        run, a subgroup): the gang holds when ``cp.min_needed`` place."""
+        self.jobs.append(JobPlan(
+            job_key=cp.job_key, class_begin=len(self.classes),
+            class_end=len(self.classes) + 1, occupied=0,
+            min_available=cp.min_needed))
+        self.classes.append(cp)
 
     def finalize(self) -> None:
         """Assign undo-log slots (one contiguous region per class),
