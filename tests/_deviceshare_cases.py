@@ -2,6 +2,8 @@
 every family the packing rule can go wrong on, and a hand-built plan with
 device classes on every route of the cycle runner."""
 
+import functools
+
 import numpy as np
 import torch
 
@@ -156,10 +158,12 @@ def device_plan_case():
     return case, requests, rules
 
 
-def build_device_plan(device):
+def build_device_plan(device, K=4):
+    """K = 4: the small plan.  K = 16: the same plan on sixteen cards, where
+    classes place on cards 8 to 15 and their words are negative as int32."""
     case, requests, rules = device_plan_case()
     plan = kc.build_plan(case, device)
-    cards = card_case(case.N, 4, 11)
+    cards = card_case(case.N, K, 11)
     plan.set_device_state(cards["mem_used"], cards["cores_used"],
                           cards["state"], cards["mem_total"])
     for c, rq in requests.items():
@@ -176,3 +180,276 @@ def build_device_plan(device):
             plan.classes[c].hypernode = plan.add_hypernode_group(
                 row, ref.hypernode_table(tiers, 6, leaves))
     return plan, requests
+
+
+# -- the integer limits of the packing kernels ------------------------------
+#
+# Values at the top of the contract (every per-unit value below 2^28, sums
+# above int32), where the per-pod oracles cannot walk: the oracle is the
+# closed form in numpy (``ref.device_*_closed``), and ``card_closed_py``
+# derives it again on plain Python integers, which cannot wrap.  The pieces
+# of that derivation (``pack_cap_py``, ``pack_fill_py``, ``pack_word``,
+# ``pack_decode``) are shared with the zone cases and take a ``wrong``
+# switch that emulates one wrong kernel, or one wrong host decode, each.
+
+TOP = (1 << 28) - 1
+INT_MAX = (1 << 31) - 1
+BIG_N = 65                      # crosses a wave boundary
+
+MUTANTS = ("S-int32", "prefix-int32", "product-int32", "mask-24",
+           "decode-sign-extends", "unroll-short", "ties-to-higher")
+WRAP_MUTANTS = ("S-int32", "prefix-int32", "product-int32")
+
+
+def _i32(x):
+    """x as a C int holds it after a wrap."""
+    return (x + (1 << 31)) % (1 << 32) - (1 << 31)
+
+
+def _cdiv(a, b):
+    """C division: towards zero."""
+    return abs(a) // b * (1 if a >= 0 else -1)
+
+
+def pack_cap_py(slots, need, cap, bounds, wrong=None):
+    """The cap kernel on one node: min(cap, S / need) or cap itself.
+    ``bounds`` are the unroll bounds of the policy, ascending."""
+    U = len(slots)
+    if wrong == "unroll-short":
+        U = min(U, next(b for b in bounds if b >= U) // 2)
+    S = sum(slots[:U])
+    if wrong == "S-int32":
+        S = _i32(S)
+    fit = _cdiv(S, need)
+    return fit if cap > 0 and fit < cap else cap
+
+
+def pack_fill_py(keys, slots, cnt, need, wrong=None):
+    """The commit kernel on one log entry: [(unit, take)] in fill order,
+    the units without a take left out."""
+    sign = -1 if wrong == "ties-to-higher" else 1
+    order = sorted((u for u in range(len(slots)) if slots[u] > 0),
+                   key=lambda u: (keys[u], sign * u))
+    want = cnt * need
+    if wrong == "product-int32":
+        want = _i32(want)
+    runs, prefix = [], 0
+    for u in order:
+        take = min(max(want - prefix, 0), slots[u])
+        prefix += slots[u]
+        if wrong == "prefix-int32":
+            prefix = _i32(prefix)
+        if take > 0:
+            runs.append((u, take))
+    return runs
+
+
+def pack_word(unit, take, wrong=None):
+    mask = (1 << 24) - 1 if wrong == "mask-24" else TOP
+    return (unit << 28 | (take & mask)) & 0xFFFFFFFF
+
+
+def pack_decode(word, wrong=None):
+    """(unit, take) of a word read as uint32; the wrong decode shifts the
+    int32."""
+    word = int(word) & 0xFFFFFFFF
+    unit = _i32(word) >> 28 if wrong == "decode-sign-extends" else word >> 28
+    return unit, word & TOP
+
+
+def _card_slots_py(mu, cu, st, total, request):
+    _, memory, cores = request
+    if st & ref.DEV_GONE:
+        return 0
+    if memory == 0 and cores == 0:
+        return 1 if st == 0 else 0
+    if mu > total:
+        return 0
+    s = []
+    if memory > 0:
+        s.append((total - mu) // memory)
+    if cores > 0:
+        s.append(_cdiv(100 - cu, cores))
+    return max(min(s), 0)
+
+
+def card_closed_py(case, request, wrong=None):
+    """cap, the assignment rows, their decoded (card, take) runs and the
+    planes after the commit of ``case``, on Python integers."""
+    count, memory, cores = request
+    mu, cu, st = (case[k].tolist()
+                  for k in ("mem_used", "cores_used", "state"))
+    total = case["mem_total"].tolist()
+    K, N = case["mem_used"].shape
+    slots = [[_card_slots_py(mu[k][n], cu[k][n], st[k][n], total[n], request)
+              for k in range(K)] for n in range(N)]
+    cap = [pack_cap_py(slots[n], count, c, (4, 8, 16), wrong)
+           for n, c in enumerate(case["cap"].tolist())]
+    rows, runs = [], []
+    for n, cnt in zip(case["log_nodes"].tolist(),
+                      case["log_counts"].tolist()):
+        fill = pack_fill_py([-m for m in (mu[k][n] for k in range(K))],
+                            slots[n], cnt, count, wrong) if cnt > 0 else []
+        words = [pack_word(k, take, wrong) for k, take in fill]
+        rows.append(words + [0] * (K - len(words)))
+        runs.append([pack_decode(w, wrong) for w in words])
+        for k, take in fill:
+            if memory == 0 and cores == 0:
+                st[k][n] = (st[k][n] + take) | ref.DEV_GONE
+            else:
+                st[k][n] += take
+                mu[k][n] += take * memory
+                cu[k][n] += take * cores
+    return dict(cap=cap, rows=rows, runs=runs, mem_used=mu, cores_used=cu,
+                state=st)
+
+
+def card_closed(case, request):
+    """The same figures from the numpy closed form of ``reference``: the
+    oracle of the GPU tests.  ``score`` and ``cap`` stay numpy."""
+    score, cap = (torch.from_numpy(case[k].copy()) for k in ("score", "cap"))
+    ref.device_cap_closed(score, cap, *planes_of(case), request)
+    planes = planes_of(case)
+    L = len(case["log_nodes"])
+    assign = torch.zeros((L, case["mem_used"].shape[0]), dtype=torch.int32)
+    ref.device_commit_closed(
+        torch.from_numpy(case["log_nodes"]),
+        torch.from_numpy(case["log_counts"]), torch.tensor(L), *planes[:4],
+        assign, request)
+    rows = assign.numpy().view(np.uint32).tolist()
+    return dict(score=score.numpy(), cap=cap.numpy().tolist(), rows=rows,
+                runs=[[pack_decode(w) for w in row if w] for row in rows],
+                mem_used=planes[0].tolist(), cores_used=planes[1].tolist(),
+                state=planes[2].tolist())
+
+
+CLOSED_KEYS = ("cap", "rows", "runs", "mem_used", "cores_used", "state")
+
+
+def _columns(patterns, N=BIG_N):
+    """[K, N]: node n holds patterns[n % len(patterns)]."""
+    return np.stack([np.asarray(patterns[n % len(patterns)], dtype=np.int64)
+                     for n in range(N)], axis=1)
+
+
+def _big_case(mem_used, cores_used, state, mem_total, caps, period):
+    """Planes as int32, and ``cap`` cycling through ``caps`` once per
+    ``period`` nodes, so that every column pattern meets every cap."""
+    N = mem_used.shape[1]
+    cap = np.asarray(caps, dtype=np.int64)[
+        (np.arange(N) // period) % len(caps)]
+    score = np.where(cap > 0, 0.5, -np.inf).astype(np.float32)
+    return dict(mem_used=mem_used.astype(np.int32),
+                cores_used=cores_used.astype(np.int32),
+                state=state.astype(np.int32),
+                mem_total=np.broadcast_to(
+                    np.asarray(mem_total, dtype=np.int32), (N,)).copy(),
+                cap=cap.astype(np.int32), score=score)
+
+
+def _set_log(case, entries):
+    nodes, counts = zip(*entries)
+    assert len(set(nodes)) == len(nodes)
+    case.update(log_nodes=np.array(nodes, dtype=np.int32),
+                log_counts=np.array(counts, dtype=np.int32))
+    return case
+
+
+def _fit_log(case, request):
+    """A log over the nodes that pack something: full, one pod and about
+    half in turn; entry 1 zeroed."""
+    fit = ref.device_slots(*planes_of(case), request).sum(0) // request[0]
+    nodes = np.nonzero(fit > 0)[0][:40]
+    entries = [(int(n), [int(fit[n]), 1, (int(fit[n]) + 1) // 2][i % 3])
+               for i, n in enumerate(nodes)]
+    entries[1] = (entries[1][0], 0)
+    return _set_log(case, entries)
+
+
+def _top_cards(request):
+    """mem_total = 2^28 - 1 and one-MiB slices on sixteen cards.  Columns,
+    node n holding pattern n % 5: A all cards empty (every key ties, the
+    fill goes by index), B mem_used[k] = k (fill order 15 .. 0), C
+    mem_used[k] = 15 - k, D only card 15 has room (the rest full), E only
+    card 8 (the rest absent).  S = 2^32 - 16 on A."""
+    k = np.arange(16)
+    mem_used = _columns([0 * k, k, 15 - k, np.where(k == 15, 0, TOP),
+                         np.where(k == 8, 0, TOP)])
+    state = (mem_used > 0).astype(np.int64)
+    state[:, 4::5] = np.where(k == 8, 0, ref.DEV_GONE)[:, None]
+    case = _big_case(mem_used, 0 * mem_used, state, TOP,
+                     [INT_MAX, 1 << 30, 5, 0], 5)
+    A, B, C, D, E = range(5)                # + 5 j: the j-th such node
+    if request[0] == 7:
+        # 14 cards hold 14 TOP slices on A and 14 TOP - 119 on B and C,
+        # both multiples of 7: those fills end on a card boundary with a
+        # prefix above 2^31; S // 7 pods leave two slices of the last card
+        log = [(A, 16 * TOP // 7), (A + 5, 2 * TOP), (A + 10, 0),
+               (B, 2 * TOP - 17), (B + 5, 300_000_000),
+               (B + 10, (16 * TOP - 120) // 7), (C, 2 * TOP - 17),
+               (C + 5, 1), (D, TOP // 7), (E, 1), (64, TOP // 7)]
+    else:
+        log = [(A, INT_MAX), (A + 5, TOP), (A + 10, 0), (B, INT_MAX),
+               (B + 5, TOP - 15), (C, 1 << 30), (D, TOP), (E, TOP), (64, 5)]
+    return _set_log(case, log)
+
+
+def _one_slot_cards(request):
+    """A slice as large as a card: memory = mem_total = 2^28 - 1 (one MiB
+    less on every fourth node, which then packs nothing): one slot on an
+    empty card, none on a card with one MiB used; take * memory at its
+    top."""
+    rng = np.random.RandomState(3)
+    mem_used = rng.choice([0, 0, 0, 1, TOP], size=(16, BIG_N))
+    state = (mem_used > 0).astype(np.int64)
+    state[rng.rand(16, BIG_N) < 0.1] = ref.DEV_GONE
+    total = np.where(np.arange(BIG_N) % 4 == 3, TOP - 1, TOP)
+    case = _big_case(mem_used, 0 * mem_used, state, total, [50, 1, 3, 0], 1)
+    return _fit_log(case, request)
+
+
+def _mid_cards(request):
+    """No power of two anywhere: 250,000,000 MiB cards and slices of 16,385
+    MiB; memory bounds some cards (50 slots, 0 slots one MiB short) and
+    cores others (100, 63, 1, 0 slots at one percent each)."""
+    total = 250_000_000
+    rng = np.random.RandomState(4)
+    mem_used = rng.choice([0, 123_456_789, total - 50 * 16_385 - 7,
+                           total - 16_384, total], size=(16, BIG_N))
+    cores_used = rng.choice([0, 37, 99, 100], size=(16, BIG_N))
+    state = (mem_used > 0).astype(np.int64) + (cores_used > 0)
+    state[rng.rand(16, BIG_N) < 0.1] = ref.DEV_GONE
+    case = _big_case(mem_used, cores_used, state, total,
+                     [INT_MAX, 1000, 3, 0], 1)
+    return _fit_log(case, request)
+
+
+def _overfull_cards(request):
+    """mem_used above mem_total, up to the top of int32: such a card is
+    over-full and has no slot; its neighbours pack as usual."""
+    rng = np.random.RandomState(6)
+    mem_used = rng.choice([0, 500, 1001, 1 << 30, INT_MAX], size=(5, BIG_N))
+    state = (mem_used > 0).astype(np.int64)
+    case = _big_case(mem_used, 0 * mem_used, state, 1000, [50, 1, 3, 0], 1)
+    return _fit_log(case, request)
+
+
+BIG_CARD_CASES = {
+    "top-1x1MiB": (_top_cards, (1, 1, 0)),
+    "top-7x1MiB": (_top_cards, (7, 1, 0)),
+    "one-slot-1": (_one_slot_cards, (1, TOP, 0)),
+    "one-slot-3": (_one_slot_cards, (3, TOP, 0)),
+    "mid-1-both": (_mid_cards, (1, 16_385, 1)),
+    "mid-3-both": (_mid_cards, (3, 16_385, 1)),
+    "mid-2-memory": (_mid_cards, (2, 16_385, 0)),
+    "overfull-1": (_overfull_cards, (1, 300, 0)),
+    "overfull-2": (_overfull_cards, (2, 100, 40)),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def big_card_case(name):
+    """(case, request, oracle): built once, never modified."""
+    build, request = BIG_CARD_CASES[name]
+    case = build(request)
+    return case, request, card_closed(case, request)

@@ -2,6 +2,8 @@
 plane that holds every family the pinning rule can go wrong on, and a
 hand-built plan with NUMA classes on every route of the cycle runner."""
 
+import functools
+
 import numpy as np
 import torch
 
@@ -97,10 +99,12 @@ def numa_plan_case():
     return case, numa, devices, rules
 
 
-def build_numa_plan(device):
+def build_numa_plan(device, Z=3):
+    """Z = 3: the small plan.  Z = 8: the same plan on eight zones, where
+    classes pin into zones 4 to 7."""
     case, numa, devices, rules = numa_plan_case()
     plan = kc.build_plan(case, device)
-    plan.set_numa_state(zone_case(case.N, 3, 11)["zone_free"])
+    plan.set_numa_state(zone_case(case.N, Z, 11)["zone_free"])
     cards = dc.card_case(case.N, 4, 11)
     plan.set_device_state(cards["mem_used"], cards["cores_used"],
                           cards["state"], cards["mem_total"])
@@ -120,3 +124,159 @@ def build_numa_plan(device):
             plan.classes[c].hypernode = plan.add_hypernode_group(
                 row, ref.hypernode_table(tiers, 6, leaves))
     return plan, numa
+
+
+# -- the integer limits of the packing kernels ------------------------------
+#
+# Zone values at the top of the contract, where the per-pod oracle cannot
+# walk.  The oracle is the closed form in numpy on ``ref.numa_slots``
+# (``numa_cap_closed`` / ``numa_commit_closed``); ``zone_closed_py`` derives
+# it again on plain Python integers from the pieces of ``_deviceshare_cases``.
+# Eight zones of 2^28 - 1 slots sum to 2^31 - 8 and a pod needs one slot, so
+# no sum or product of this policy leaves int32 and no word has its sign bit
+# set: of ``dc.MUTANTS`` only the three below differ from the right kernel
+# on a legitimate zone plane.
+
+TOP, INT_MAX, BIG_N = dc.TOP, dc.INT_MAX, dc.BIG_N
+MUTANTS = ("mask-24", "unroll-short", "ties-to-higher")
+
+
+def numa_cap_closed(score, cap, zone_free, cpu):
+    """``numa_cap`` in closed form on numpy arrays, in place."""
+    S = ref.numa_slots(torch.from_numpy(zone_free), cpu).sum(0)
+    hit = (cap > 0) & (S < cap)
+    cap[hit] = S[hit]
+    score[hit & (S == 0)] = -np.inf
+
+
+def numa_commit_closed(log_nodes, log_counts, zone_free, rows, cpu):
+    """``numa_commit`` in closed form on numpy arrays, in place: zones with
+    slots fill in the order (free asc, index asc), each taking
+    ``clamp(cnt - prefix, 0, slots)``."""
+    slots = ref.numa_slots(torch.from_numpy(zone_free), cpu)
+    Z = zone_free.shape[0]
+    words = rows.view(np.uint32)
+    for e, (n, cnt) in enumerate(zip(log_nodes.tolist(),
+                                     log_counts.tolist())):
+        words[e] = 0
+        if cnt <= 0:
+            continue
+        order = [z for z in np.lexsort((np.arange(Z), zone_free[:, n]))
+                 if slots[z, n] > 0]
+        s = slots[order, n]
+        take = np.clip(cnt - (np.cumsum(s) - s), 0, s)
+        for p, (z, t) in enumerate(zip(order, take.tolist())):
+            if t > 0:
+                words[e, p] = (int(z) << ref.NUMA_TAKE_BITS) | t
+                zone_free[z, n] -= t * cpu
+
+
+def zone_closed(case, cpu):
+    """cap, rows, decoded runs and the plane after the commit of ``case``
+    from the numpy closed form: the oracle of the GPU tests."""
+    score, cap, free = (case[k].copy() for k in ("score", "cap", "zone_free"))
+    numa_cap_closed(score, cap, case["zone_free"], cpu)
+    rows = np.zeros((len(case["log_nodes"]), free.shape[0]), dtype=np.int32)
+    numa_commit_closed(case["log_nodes"], case["log_counts"], free, rows, cpu)
+    rows = rows.view(np.uint32).tolist()
+    return dict(score=score, cap=cap.tolist(), rows=rows,
+                runs=[[dc.pack_decode(w) for w in row if w] for row in rows],
+                zone_free=free.tolist())
+
+
+CLOSED_KEYS = ("cap", "rows", "runs", "zone_free")
+
+
+def zone_closed_py(case, cpu, wrong=None):
+    """The same figures on Python integers."""
+    free = case["zone_free"].tolist()
+    Z, N = case["zone_free"].shape
+    slots = [[free[z][n] // cpu if free[z][n] > 0 else 0 for z in range(Z)]
+             for n in range(N)]
+    cap = [dc.pack_cap_py(slots[n], 1, c, (2, 4, 8), wrong)
+           for n, c in enumerate(case["cap"].tolist())]
+    rows, runs = [], []
+    for n, cnt in zip(case["log_nodes"].tolist(),
+                      case["log_counts"].tolist()):
+        fill = dc.pack_fill_py([free[z][n] for z in range(Z)], slots[n], cnt,
+                               1, wrong) if cnt > 0 else []
+        words = [dc.pack_word(z, take, wrong) for z, take in fill]
+        rows.append(words + [0] * (Z - len(words)))
+        runs.append([dc.pack_decode(w, wrong) for w in words])
+        for z, take in fill:
+            free[z][n] -= take * cpu
+    return dict(cap=cap, rows=rows, runs=runs, zone_free=free)
+
+
+def _big_case(free, caps, period):
+    N = free.shape[1]
+    cap = np.asarray(caps, dtype=np.int64)[
+        (np.arange(N) // period) % len(caps)]
+    score = np.where(cap > 0, 0.5, -np.inf).astype(np.float32)
+    return dict(zone_free=free.astype(np.int32), cap=cap.astype(np.int32),
+                score=score)
+
+
+def _fit_log(case, cpu, policy):
+    """A log over the first 40 nodes: all S pods, one, and about half in
+    turn (0 where S is 0), two more each under best-effort; entry 1
+    zeroed."""
+    S = ref.numa_slots(torch.from_numpy(case["zone_free"]), cpu).sum(0)
+    over = 2 if policy == SOFT else 0
+    entries = [(n, [int(S[n]), min(int(S[n]), 1), (int(S[n]) + 1) // 2][n % 3]
+                + over) for n in range(40)]
+    entries[1] = (1, 0)
+    return dc._set_log(case, entries)
+
+
+def _top_zones(Z, cpu, policy):
+    """free = 2^28 - 1 and pods of one millicore.  Columns, node n holding
+    pattern n % 4: A every zone at the top (all keys tie, the fill goes by
+    index), B free[z] = top - z (fill order Z - 1 .. 0), C the reverse, D
+    only the last zone has room.  S = 2^31 - 8 on A at Z = 8."""
+    z = np.arange(Z)
+    free = dc._columns([TOP + 0 * z, TOP - z, TOP - (Z - 1 - z),
+                        np.where(z == Z - 1, TOP, 0)])
+    case = _big_case(free, [INT_MAX, 1 << 30, 5, 0], 4)
+    A, B, C, D = range(4)                   # + 4 j: the j-th such node
+    S, S_B = Z * TOP, Z * TOP - Z * (Z - 1) // 2
+    if policy == HARD:
+        # C's first zone in fill order is zone 0: that fill ends on its brim
+        log = [(A, S), (A + 4, S - 1), (A + 8, 0), (B, S_B), (B + 4, S_B - 1),
+               (C, TOP - (Z - 1)), (C + 4, 1 << 24), (D, TOP), (64, 5)]
+    else:
+        log = [(A, S + 2), (A + 4, INT_MAX), (A + 8, 0), (B, S_B + 2),
+               (B + 4, INT_MAX), (C, INT_MAX), (D, TOP + 1), (64, S + 2)]
+    return dc._set_log(case, log)
+
+
+def _one_slot_zones(Z, cpu, policy):
+    """A pod as large as a zone (cpu = 2^28 - 1): one slot at the top
+    value, none one millicore below it."""
+    free = np.random.RandomState(3).choice([TOP, TOP, TOP - 1, 0],
+                                           size=(Z, BIG_N))
+    return _fit_log(_big_case(free, [50, 1, 3, 0], 1), cpu, policy)
+
+
+def _odd_zones(Z, cpu, policy):
+    """No power of two: pods of 16,385 millicores on zones from one slot
+    (and one millicore short of it) to the top."""
+    free = np.random.RandomState(4).choice(
+        [TOP, 250_000_000, 123_456_789, 16_385, 16_384, 0], size=(Z, BIG_N))
+    return _fit_log(_big_case(free, [INT_MAX, 1000, 3, 0], 1), cpu, policy)
+
+
+BIG_ZONE_CASES = {
+    f"{name}-Z{Z}": (build, Z, cpu)
+    for name, build, cpu in (("top", _top_zones, 1),
+                             ("one-slot", _one_slot_zones, TOP),
+                             ("cpu16385", _odd_zones, 16_385))
+    for Z in (8, 5)}
+
+
+@functools.lru_cache(maxsize=None)
+def big_zone_case(name, policy):
+    """(case, cpu, oracle): built once, never modified."""
+    build, Z, cpu = BIG_ZONE_CASES[name]
+    case = build(Z, cpu, policy)
+    return case, cpu, zone_closed(case, cpu)

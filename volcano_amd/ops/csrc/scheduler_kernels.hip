@@ -1390,10 +1390,17 @@ struct PackUnit { int slots, key; };
 //     function of that card alone.
 //   * order: the chosen card only gets fuller, so it stays the strict
 //     maximum.  The key is ~mem_used: a decreasing bijection of int32, so
-//     key asc is mem_used desc for EVERY int32 mem_used (nothing range-checks
-//     that plane; only mem_total < 2^28 is host-checked).
+//     key asc is mem_used desc.
 // card_state is the slice count with DS_GONE set for an exclusive or absent
-// card.
+// card.  Host-checked ranges of the planes (plan.set_device_state; a pool
+// outside them keeps the host path): 0 <= mem_total < 2^28, mem_used >= 0,
+// cores_used >= 0, slice count in [0, 2^28).  What follows: a card with
+// mem_used > mem_total is over-full and has no slot; on every other card
+// total - mu lies in [0, 2^28) and 100 - cu in (-2^31, 100], so neither
+// subtraction overflows, slots < 2^28, take * memory <= total - mu and
+// take * cores <= 100.  The order of the key holds for every int32; the
+// slots do not (a negative mem_used can give 2^28 slots or more, whose take
+// would carry into the card field of its word), hence the check.
 struct CardPolicy {
     static constexpr int WIDTH = 16;
     int* mem_used;

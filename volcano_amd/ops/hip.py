@@ -322,7 +322,11 @@ _ZONES = (NUMA_MAX_ZONES,) + 3 * (
 def _unit_planes(op, family, planes, per_node=None):
     """(U, N) of the unit planes of a family, checked: contiguous int32
     [U, N], 1 <= U <= limit, all the same shape (``per_node``: [N]).
-    Plain loops: this runs in front of every launch."""
+    Plain loops: this runs in front of every launch.  The planes live on
+    the device, so what they HOLD is the caller's precondition, checked
+    where they are built from host arrays (``plan.set_device_state``,
+    ``plan.set_numa_state``): 0 <= mem_total < 2^28, mem_used >= 0,
+    cores_used >= 0, a slice count in [0, 2^28); 0 <= zone_free < 2^28."""
     limit, bad_rank, bad_shape, bad_layout = family
     shape = planes[0].shape
     if len(shape) != 2 or not 1 <= shape[0] <= limit:

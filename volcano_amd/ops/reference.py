@@ -555,6 +555,22 @@ def check_device_request(request):
     return count, memory, cores
 
 
+def check_card_planes(mem_used, cores_used, state) -> None:
+    """ValueError unless the numpy card planes hold what the packing rule
+    is closed form on: ``mem_used >= 0`` (with ``mem_total < 2^28`` that
+    keeps ``mem_total - mem_used`` of a card that is not over-full in
+    [0, 2^28), hence its slots below 2^28), ``cores_used >= 0`` and a
+    slice count ``state & ~DEV_GONE`` in [0, 2^28).  ``mem_used`` above
+    ``mem_total`` is an over-full card: no slots, nothing wrong."""
+    if mem_used.min(initial=0) < 0:
+        raise ValueError("device state: mem_used below 0")
+    if cores_used.min(initial=0) < 0:
+        raise ValueError("device state: cores_used below 0")
+    slices = state & ~DEV_GONE
+    if slices.min(initial=0) < 0 or slices.max(initial=0) >= DEV_MEM_LIMIT:
+        raise ValueError("device state: slice count outside [0, 2^28)")
+
+
 def _device_pool(mem_used, cores_used, state, mem_total, n):
     """Node n's cards as a GPUDevicePool (an absent card can never be
     taken, like an exclusive one)."""

@@ -317,6 +317,7 @@ class CyclePlan:
         if mem_total.max(initial=0) >= ref.DEV_MEM_LIMIT or \
                 mem_total.min(initial=0) < 0:
             raise ValueError("device state: mem_total outside [0, 2^28)")
+        ref.check_card_planes(*planes)
         self.device_state = DeviceState(*planes, mem_total)
 
     def add_device_request(self, cp: ClassPlan, count: int, memory: int,

@@ -20,8 +20,9 @@ bit; the cycle then packs per card, per placement (``device_cap`` /
 instead of choosing again.  The pools stay the ledger across cycles.
 
 ``exact`` stays on the host path (logged once) for an inventory with a node
-above 16 cards or a card of 2^28 MiB or more, and is ignored under the
-soft-shard coordinator and by preempt/reclaim."""
+above 16 cards, a card of 2^28 MiB or more, or a card whose ledger holds
+what the planes do not (negative usage, 2^28 slices or more), and is
+ignored under the soft-shard coordinator and by preempt/reclaim."""
 
 from __future__ import annotations
 
@@ -76,7 +77,9 @@ class DeviceExact:
 
 def card_planes(pools, nodes, n: int):
     """The pools as int32 card planes [K, N] + mem_total [N], or None when
-    the inventory does not fit them (K > 16, a card of >= 2^28 MiB)."""
+    the inventory does not fit them (K > 16, a card of >= 2^28 MiB, a card
+    with negative usage or with 2^28 slices or more: the ranges
+    ``plan.set_device_state`` checks)."""
     K = max((len(p.cards) for p in pools.values()), default=0)
     if K == 0 or K > DEV_MAX_CARDS:
         return None
@@ -94,6 +97,10 @@ def card_planes(pools, nodes, n: int):
             return None
         mem_total[ni.node_id] = total
         for k, c in enumerate(pool.cards):
+            if not 0 <= c.mem_used < 1 << 31 or \
+                    not 0 <= c.cores_used < 1 << 31 or \
+                    not 0 <= c.slices < DEV_MEM_LIMIT:
+                return None
             mem_used[k, ni.node_id] = c.mem_used
             cores_used[k, ni.node_id] = c.cores_used
             state[k, ni.node_id] = c.slices | (DEV_GONE if c.exclusive else 0)
@@ -164,7 +171,8 @@ class DeviceSharePlugin(Plugin):
                     log.warning(
                         "deviceshare: exact is off — the inventory has a "
                         "node above %d cards, cards of unequal size on one "
-                        "node or a card of 2^28 MiB or more; per-card "
+                        "node, a card of 2^28 MiB or more, or a card with "
+                        "negative usage or 2^28 slices or more; per-card "
                         "packing stays on the host path", DEV_MAX_CARDS)
 
         def take_chosen(pool, req, cards):
