@@ -108,6 +108,9 @@ struct ClassView {
     const int32_t* dev;
     // NUMA request (cpu millicores, policy); null = none
     const int32_t* numa;
+    // every rule of a spread class that has several (multi.n >= 2, rule 0
+    // being the one above); n == 0 otherwise
+    VamdSpreadRules multi;
 };
 
 struct Runner {
@@ -166,7 +169,7 @@ struct Runner {
             cy.log_nodes + cd.log_off, cy.log_counts + cd.log_off,
             cy.log_len + c, cy.class_placed + c, cy.job_placed + j,
             cy.job_flag + j, single ? gang_fuse_min(job, cd) : -1,
-            g, 0, 0, 0, nullptr, nullptr, dev_of(c), numa_of(c)};
+            g, 0, 0, 0, nullptr, nullptr, dev_of(c), numa_of(c), {}};
         if (g >= 0) {
             v.mode = cy.class_mode != nullptr ? cy.class_mode[c] : 0;
             if (v.mode == 0) v.skew = cy.class_skew[c];
@@ -174,6 +177,19 @@ struct Runner {
             const int row = cy.group_row != nullptr ? cy.group_row[g] : g;
             v.dom_of = cy.dom_of + (size_t)row * cy.N;
             v.dom_count = cy.count + cy.count_off[g];
+        }
+        if (g >= 0 && v.mode == 0 && cy.class_spread_rules != nullptr) {
+            const int32_t* row = cy.class_spread_rules + (size_t)c * 9;
+            const int n = row[0] >= 2 && row[0] <= VAMD_SPREAD_MAX_RULES
+                ? row[0] : 0;
+            for (int k = 0; k < n; ++k) {
+                const int gk = row[1 + 2 * k];
+                const int rk = cy.group_row != nullptr ? cy.group_row[gk] : gk;
+                v.multi.r[k] = {cy.dom_of + (size_t)rk * cy.N,
+                                cy.count + cy.count_off[gk], cy.domains[gk],
+                                row[2 + 2 * k]};
+            }
+            v.multi.n = n;
         }
         return v;
     }
@@ -211,6 +227,15 @@ struct Runner {
                            v.job_placed, v.dom_of, v.dom_count, v.D, v.skew,
                            v.fuse_min, cy.domain_scratch, cy.N, cy.R,
                            v.cd.log_cap, stream);
+    }
+
+    void spread_multi_select(const ClassView& v) const {
+        // slot: the first 4*N bytes of the domain scratch
+        vamd_spread_multi_select(
+            cy.score_scratch, cy.cap_scratch, v.req, v.cd.ntasks, cy.used,
+            v.queue_alloc, v.queue_limit, v.log_nodes, v.log_counts,
+            v.log_len, v.placed, v.job_placed, v.multi, v.fuse_min,
+            cy.domain_scratch, cy.N, cy.R, v.cd.log_cap, stream);
     }
 
     void domain_mask(const ClassView& v) const {
@@ -267,6 +292,11 @@ struct Runner {
                 v.dev[2], cy.card_K, cy.N, v.cd.log_cap, stream);
         // a network-topology class holds a table, not counts: plain revert
         if (v.group >= 0 && v.mode != MODE_HYPERNODE) {
+            // rules 1..n-1 first, while the log still holds its counts
+            if (v.multi.n >= 2)
+                vamd_spread_multi_count_sub(v.job_flag, v.log_nodes,
+                                            v.log_counts, v.log_len, v.multi,
+                                            cy.N, v.cd.log_cap, stream);
             vamd_spread_revert(v.job_flag, v.log_nodes, v.log_counts,
                                v.log_len, v.req, cy.used, v.queue_alloc,
                                v.placed, v.job_placed, v.dom_of, v.dom_count,
@@ -301,8 +331,10 @@ struct Runner {
         if (v.group >= 0 && v.mode == 0) {
             // topology spread: eligibility moves with every single
             // placement, so always the spread select, whatever the class
-            // size
-            spread_select(v);
+            // size; with several rules the node-scan select that intersects
+            // them
+            if (v.multi.n >= 2) spread_multi_select(v);
+            else spread_select(v);
         } else {
             // inter-pod affinity / keyed anti-affinity / network topology:
             // the rule collapses into a mask over score/cap (from the

@@ -981,6 +981,283 @@ __global__ void spread_revert_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// K2 select under SEVERAL topology-spread constraints at once (zone AND
+// hostname, ...) — oracle: reference.py spread_multi_select_commit.  A node
+// is eligible only in the intersection of the rules' open domains, so the
+// per-domain heads of spread_select_kernel mean nothing here: the best node
+// of a zone may sit on a closed host.  This kernel keeps eligibility per
+// DOMAIN as one bit and finds the winner by scanning the NODES:
+//
+//   * s_open holds open_r[d] = (count_r[d] + 1 - m_r <= skew_r), the rules'
+//     bitmaps back to back (each starting on a 64-bit word): 32 KB of LDS,
+//     sum of D_r <= SM_LDS_DOMAINS.  The counts stay in global memory.
+//   * per rule, thread 0 owns m_r = min(count_r) and atmin_r = #domains at
+//     m_r.  A placement into a domain at the minimum decrements atmin_r; at 0
+//     the minimum is m_r + 1 (counts move by one) and the rule is flagged for
+//     a recount.  Nothing is recounted otherwise.
+//   * one iteration: every thread walks its 1024-stride slice of the nodes; a
+//     node with a score whose bit is set under every rule offers its key; ONE
+//     64-bit block max reduce; thread 0 places the winner (log, cap
+//     countdown, count_r[d]++ and the closing bit per rule) and publishes go
+//     together with the recount mask.
+//   * recount of a flagged rule, block-uniform after the barrier: a wave
+//     takes 64 consecutive domains per step, one ballot is their two bitmap
+//     words (lane 0 stores them), and a block sum is the new atmin_r.  The
+//     initial bitmaps and atmin_r come from the same code.
+//
+// Barrier conventions of dev_select_commit: thread 0 owns every counter
+// and publishes go/recount together; loop exits are read block-uniformly
+// after a barrier; no barrier under divergent control flow.
+// ---------------------------------------------------------------------------
+#define SM_RULES VAMD_SPREAD_MAX_RULES
+#define SM_LDS_WORDS 8192                   // 32 KB of eligibility bits
+#define SM_LDS_DOMAINS (SM_LDS_WORDS * 32)  // sum of D over the rules
+
+DEVINL bool sm_open(const unsigned* bits, int d) {
+    return (bits[d >> 5] >> (d & 31)) & 1u;
+}
+
+// Rebuild bitmap and atmin of the rules in `mask` against their current
+// minimum s_m[r].  Whole block; the per-wave partial sums land in s_part,
+// which thread 0 folds after the caller's barrier.
+DEVINL void sm_recount(const VamdSpreadRules& rules, int mask,
+                       unsigned* s_open, const int* s_base, const int* s_m,
+                       int (*s_part)[SP_WAVES])
+{
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wid = threadIdx.x / WAVE;
+    // r is block-uniform: the rule is read from the kernel arguments by
+    // index, so only the node walk keeps rule fields in registers
+    for (int r = 0; r < rules.n; ++r) {
+        if (!((mask >> r) & 1)) continue;
+        const int* __restrict__ count = rules.r[r].count;
+        const int D = rules.r[r].D;
+        const int skew = rules.r[r].skew;
+        const int m = s_m[r];
+        unsigned* bits = s_open + s_base[r];
+        int at = 0;
+        for (int d0 = wid * WAVE; d0 < D; d0 += SP_THREADS) {
+            const int d = d0 + lane;
+            const int c = d < D ? count[d] : INT32_MAX;
+            const bool open = d < D && c - m < skew;   // c + 1 - m <= skew
+            const unsigned long long b = __ballot(open);
+            at += (c == m) ? 1 : 0;
+            if (lane == 0) {
+                bits[d0 >> 5] = (unsigned)b;
+                bits[(d0 >> 5) + 1] = (unsigned)(b >> 32);
+            }
+        }
+        for (int off = WAVE / 2; off > 0; off >>= 1)
+            at += __shfl_down(at, off);
+        if (lane == 0) s_part[r][wid] = at;
+    }
+}
+
+// thread 0, after the barrier that follows sm_recount
+DEVINL void sm_fold(int mask, int* s_atmin, int (*s_part)[SP_WAVES]) {
+    for (int r = 0; r < SM_RULES; ++r) {
+        if (!((mask >> r) & 1)) continue;
+        int at = 0;
+        for (int w = 0; w < SP_WAVES; ++w) at += s_part[r][w];
+        s_atmin[r] = at;
+    }
+}
+
+__global__ void __launch_bounds__(SP_THREADS)
+spread_multi_select_kernel(
+    float* __restrict__ score,        // [N] consumed
+    int* __restrict__ cap,            // [N] consumed (remaining capacity)
+    const float* __restrict__ req,    // [R]
+    int ntasks,
+    float* __restrict__ used,         // [R, N] in place
+    float* __restrict__ queue_alloc,  // [R] in place
+    const float* __restrict__ queue_limit, // [R]
+    int* __restrict__ log_nodes,      // [K]
+    int* __restrict__ log_counts,     // [K]
+    int* __restrict__ log_len,        // [1]
+    int* __restrict__ placed,         // [1]
+    int* __restrict__ job_placed,     // [1]
+    const VamdSpreadRules rules,      // by value: dom_of / count / D / skew
+    int fuse_min,
+    int* __restrict__ slot,           // [N] scratch: node -> log entry
+    int N, int R, int K)
+{
+    __shared__ unsigned s_open[SM_LDS_WORDS + 2 * SM_RULES];
+    __shared__ unsigned long long s_wkey[SP_WAVES];
+    __shared__ int s_part[SM_RULES][SP_WAVES];
+    __shared__ int s_base[SM_RULES];    // word offset of rule r's bitmap
+    __shared__ int s_m[SM_RULES];       // min(count_r) for the coming iteration
+    __shared__ int s_atmin[SM_RULES];   // #domains of rule r sitting at s_m[r]
+    __shared__ int s_budget;
+    __shared__ int s_cursor;
+    __shared__ int s_total;
+    __shared__ int s_go;
+    __shared__ int s_recount;           // mask of rules whose minimum rose
+
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wid = tid / WAVE;
+    const int n_rules = rules.n;
+    const int all_rules = (1 << n_rules) - 1;
+
+    if (tid == 0) {
+        long long b = dev_queue_budget(req, queue_limit, queue_alloc, ntasks,
+                                       R);
+        s_budget = (n_rules > 0 && b > 0) ? (int)b : 0;
+        s_cursor = 0;
+        s_total = 0;
+        // a wave step of the recount covers 64 domains = two words
+        int base = 0;
+        for (int r = 0; r < n_rules; ++r) {
+            s_base[r] = base;
+            base += 2 * ((rules.r[r].D + WAVE - 1) / WAVE);
+        }
+    }
+
+    // nodes that can never take an instance leave the score vector
+    for (int i = tid; i < N; i += SP_THREADS) {
+        slot[i] = -1;
+        bool ok = score[i] > NEG_INF && cap[i] > 0;
+        for (int r = 0; r < n_rules; ++r) {
+            const int d = rules.r[r].dom_of[i];
+            ok = ok && d >= 0 && d < rules.r[r].D;
+        }
+        if (!ok) score[i] = NEG_INF;
+    }
+
+    // initial minimum per rule: per-wave partial minima, folded by thread 0
+    for (int r = 0; r < n_rules; ++r) {
+        int lmin = INT32_MAX;
+        for (int d = tid; d < rules.r[r].D; d += SP_THREADS)
+            lmin = min(lmin, rules.r[r].count[d]);
+        for (int off = WAVE / 2; off > 0; off >>= 1)
+            lmin = min(lmin, __shfl_down(lmin, off));
+        if (lane == 0) s_part[r][wid] = lmin;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int r = 0; r < n_rules; ++r) {
+            int m = INT32_MAX;
+            for (int w = 0; w < SP_WAVES; ++w) m = min(m, s_part[r][w]);
+            s_m[r] = m;
+        }
+    }
+    __syncthreads();
+    sm_recount(rules, all_rules, s_open, s_base, s_m, s_part);
+    __syncthreads();
+    if (tid == 0) sm_fold(all_rules, s_atmin, s_part);
+
+    const int budget = s_budget;
+    for (int it = 0; it < budget; ++it) {
+        unsigned long long loc = 0ull;
+        // the score and the domain ids are loaded unconditionally, four
+        // nodes in flight, so that the loads overlap
+#pragma unroll 4
+        for (int i = tid; i < N; i += SP_THREADS) {
+            const float s = score[i];
+            int dom[SM_RULES];
+#pragma unroll
+            for (int r = 0; r < SM_RULES; ++r)
+                dom[r] = r < n_rules ? rules.r[r].dom_of[i] : 0;
+            // only a live node has its domains inside [0, D_r)
+            const bool live = s > NEG_INF;
+            bool open = live;
+#pragma unroll
+            for (int r = 0; r < SM_RULES; ++r)
+                if (r < n_rules)
+                    open &= sm_open(s_open + s_base[r], live ? dom[r] : 0);
+            if (open) {
+                const unsigned long long k = spread_key(s, i);
+                if (k > loc) loc = k;
+            }
+        }
+        loc = wave_max_u64(loc);
+        if (lane == 0) s_wkey[wid] = loc;
+        __syncthreads();
+        if (wid == 0) {
+            unsigned long long k = lane < SP_WAVES ? s_wkey[lane] : 0ull;
+            for (int off = SP_WAVES / 2; off > 0; off >>= 1) {
+                unsigned long long o = __shfl_down(k, off);
+                k = o > k ? o : k;
+            }
+            // lane 0 of wave 0 is thread 0, the only writer of the counters,
+            // the log, the counts, cap, the closing bits and s_m / s_atmin
+            if (lane == 0) {
+                int go = 0, recount = 0;
+                if (k != 0ull) {
+                    const int node = spread_key_node(k);
+                    int sl = slot[node];
+                    if (sl >= 0 || s_cursor < K) {
+                        go = 1;
+                        // one thread, a uniform r: the rule is read from
+                        // the kernel arguments by index, not unrolled
+                        for (int r = 0; r < n_rules; ++r) {
+                            const int d = rules.r[r].dom_of[node];
+                            const int c = rules.r[r].count[d];
+                            const int m = s_m[r];
+                            rules.r[r].count[d] = c + 1;
+                            // one more would break the skew: shut
+                            if (c + 2 - m > rules.r[r].skew)
+                                s_open[s_base[r] + (d >> 5)] &=
+                                    ~(1u << (d & 31));
+                            // the last domain at the minimum moved up
+                            if (c == m && --s_atmin[r] == 0) {
+                                s_m[r] = m + 1;
+                                recount |= 1 << r;
+                            }
+                        }
+                        if (sl < 0) {
+                            sl = s_cursor;
+                            s_cursor = sl + 1;
+                            slot[node] = sl;
+                            log_nodes[sl] = node;
+                            log_counts[sl] = 1;
+                        } else {
+                            log_counts[sl] += 1;
+                        }
+                        const int left = cap[node] - 1;
+                        cap[node] = left;
+                        if (left <= 0) score[node] = NEG_INF;
+                        s_total += 1;
+                    }
+                }
+                s_go = go;
+                s_recount = recount;
+            }
+        }
+        __syncthreads();
+        if (!s_go) break;               // block-uniform
+        const int rc = s_recount;       // block-uniform
+        if (rc != 0) {
+            sm_recount(rules, rc, s_open, s_base, s_m, s_part);
+            __syncthreads();
+            if (tid == 0) sm_fold(rc, s_atmin, s_part);
+        }
+    }
+
+    __syncthreads();
+    const int total = s_total;
+    const int cursor = s_cursor;
+    const bool revert = (fuse_min >= 0) && (total < fuse_min);
+
+    if (revert) {
+        // single-class gang failed: nothing was applied to `used` yet; give
+        // the placements back to the counts of every rule
+        for (int e = tid; e < cursor; e += SP_THREADS) {
+            const int node = log_nodes[e];
+            const int cnt = log_counts[e];
+            for (int r = 0; r < n_rules; ++r)
+                atomicSub(rules.r[r].count + rules.r[r].dom_of[node], cnt);
+            log_counts[e] = 0;
+        }
+        if (tid == 0) { *log_len = cursor; *placed = 0; }
+    } else {
+        dev_commit_log(log_nodes, log_counts, cursor, total, req, used,
+                       queue_alloc, log_len, placed, job_placed, N, R);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Inter-pod (anti-)affinity over a topology key, enforced before EVERY
 // placement — oracle: reference.py affinity_select_commit.  Unlike spread
 // this needs no per-instance loop: for both modes the per-placement rule
@@ -1345,6 +1622,34 @@ __global__ void domain_count_add_kernel(
         if (cnt <= 0 || node < 0 || node >= N) continue;
         const int d = dom_of[node];
         if (d >= 0 && d < D) atomicAdd(dom_count + d, cnt);
+    }
+}
+
+// The mirror, for the multi-class revert of a class with several spread
+// rules: when the job's flag says revert, the logged placements leave the
+// counts of rules 1..n-1 (integer atomics).  Runs while the log is intact;
+// spread_revert_kernel then does the same for rule 0 and zeroes the log.
+__global__ void domain_count_sub_kernel(
+    const uint8_t* __restrict__ flag, const int* __restrict__ log_nodes,
+    const int* __restrict__ log_counts, const int* __restrict__ log_len,
+    const VamdSpreadRules rules, int N, int K)
+{
+    if (*flag) return;
+    int len = *log_len;
+    if (len > K) len = K;
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < len;
+         e += gridDim.x * blockDim.x) {
+        const int cnt = log_counts[e];
+        const int node = log_nodes[e];
+        if (cnt <= 0 || node < 0 || node >= N) continue;
+#pragma unroll
+        for (int r = 1; r < SM_RULES; ++r) {
+            if (r < rules.n) {
+                const int d = rules.r[r].dom_of[node];
+                if (d >= 0 && d < rules.r[r].D)
+                    atomicSub(rules.r[r].count + d, cnt);
+            }
+        }
     }
 }
 
@@ -2221,6 +2526,44 @@ void vamd_domain_count_add(
                        dim3(threads), 0, stream, log_nodes, log_counts,
                        log_len, dom_of, dom_count, D, N, K);
 }
+
+void vamd_spread_multi_select(
+    float* score, int* cap, const float* req, int ntasks, float* used,
+    float* queue_alloc, const float* queue_limit, int* log_nodes,
+    int* log_counts, int* log_len, int* placed, int* job_placed,
+    VamdSpreadRules rules, int fuse_min, void* slot, int N, int R, int K,
+    hipStream_t stream)
+{
+    // the callers validate the rules (ops/hip.py raises).  A set that does
+    // not fit the LDS bitmaps must never reach them: it is launched with no
+    // rule at all, which has no budget, places nothing and writes
+    // *log_len = 0 and *placed = 0
+    long long domains = 0;
+    for (int r = 0; r < rules.n && r < SM_RULES; ++r)
+        domains += rules.r[r].D > 0 ? rules.r[r].D : SM_LDS_DOMAINS + 1;
+    if (rules.n < 1 || rules.n > SM_RULES || domains > SM_LDS_DOMAINS)
+        rules.n = 0;
+    hipLaunchKernelGGL(vamd::spread_multi_select_kernel, dim3(1),
+                       dim3(SP_THREADS), 0, stream, score, cap, req, ntasks,
+                       used, queue_alloc, queue_limit, log_nodes, log_counts,
+                       log_len, placed, job_placed, rules, fuse_min,
+                       (int*)slot, N, R, K);
+}
+
+void vamd_spread_multi_count_sub(
+    const uint8_t* flag, const int* log_nodes, const int* log_counts,
+    const int* log_len, VamdSpreadRules rules, int N, int K,
+    hipStream_t stream)
+{
+    int threads = 256;
+    int blocks = min((K + threads - 1) / threads, 64);
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(vamd::domain_count_sub_kernel, dim3(blocks),
+                       dim3(threads), 0, stream, flag, log_nodes, log_counts,
+                       log_len, rules, N, K);
+}
+
+int vamd_spread_multi_lds_domains(void) { return SM_LDS_DOMAINS; }
 
 int vamd_device_max_cards(void) { return vamd::CardPolicy::WIDTH; }
 

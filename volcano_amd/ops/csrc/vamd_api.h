@@ -106,6 +106,54 @@ void vamd_domain_count_add(
     const int* dom_of, int* dom_count, int D, int N, int K,
     hipStream_t stream);
 
+// --- several topology-spread rules per class ---------------------------------
+//
+// Up to VAMD_SPREAD_MAX_RULES rules, passed by value: a node may take an
+// instance only while EVERY rule's count[dom_of[n]] + 1 - min(count) <= skew
+// holds, so it is eligible in the intersection of the rules' open domains.
+#define VAMD_SPREAD_MAX_RULES 4
+
+struct VamdSpreadRule {
+    const int32_t* dom_of;   // [N] node -> domain id of this rule, -1 = no label
+    int32_t* count;          // [D] group members per domain, in place
+    int32_t D;               // in [1, N]
+    int32_t skew;            // >= 1
+};
+
+struct VamdSpreadRules {
+    VamdSpreadRule r[VAMD_SPREAD_MAX_RULES];
+    int32_t n;               // rules in use, 1..VAMD_SPREAD_MAX_RULES
+    int32_t _pad;
+};
+
+// The two launchers are weak, like the pack launchers: a program that links
+// the runner alone leaves class_spread_rules unset and never calls them.
+
+// vamd_spread_select under rules.n rules at once (after vamd_score_cap; ONE
+// workgroup).  Every placement joins the counts of every rule; a fused gang
+// that misses fuse_min gives them all back.  The domains' eligibility bits
+// live in LDS: sum of D over the rules <= vamd_spread_multi_lds_domains().
+// `slot` holds 4*N bytes.  With one rule the result is that of
+// vamd_spread_select.  A rule set outside these limits places nothing:
+// *log_len = 0 and *placed = 0.
+__attribute__((weak)) void vamd_spread_multi_select(
+    float* score, int* cap, const float* req, int ntasks, float* used,
+    float* queue_alloc, const float* queue_limit, int* log_nodes,
+    int* log_counts, int* log_len, int* placed, int* job_placed,
+    VamdSpreadRules rules, int fuse_min, void* slot, int N, int R, int K,
+    hipStream_t stream);
+
+// When *flag == 0: the log (e < *log_len <= K) leaves the counts of rules
+// 1..n-1.  Runs BEFORE vamd_spread_revert, which gives rule 0 its counts back
+// and zeroes the log.
+__attribute__((weak)) void vamd_spread_multi_count_sub(
+    const uint8_t* flag, const int* log_nodes, const int* log_counts,
+    const int* log_len, VamdSpreadRules rules, int N, int K,
+    hipStream_t stream);
+
+// Largest sum of D over the rules of one vamd_spread_multi_select.
+__attribute__((weak)) int vamd_spread_multi_lds_domains(void);
+
 // --- per-unit packing: GPU slices on cards, CPU requests on NUMA zones ------
 //
 // A pod takes its request from the units of a node; the rule is the host's
@@ -308,6 +356,11 @@ struct VamdCycle {
     int32_t* numa_assign;          // [L, zone_Z], parallel to the log
     int32_t zone_Z;
     int32_t _pad3;
+    // several spread rules per class: live when set (and the domain-rule
+    // block is).  Row c is n, then VAMD_SPREAD_MAX_RULES (group, maxSkew)
+    // pairs; the class is multi-rule when n >= 2 and then also carries rule 0
+    // in class_group / class_skew with mode 0
+    const int32_t* class_spread_rules;  // HOST [C, 9]
 };
 
 // Device copies of the descriptor arrays (chain and megacycle paths).
@@ -346,6 +399,11 @@ void vamd_megacycle(const VamdCycle& cy, const VamdDevDescs& dd,
 //     vamd_score_cap + vamd_spread_select — never the fused, bulk, chain
 //     or megacycle path — and reverts through vamd_spread_revert.  Counts
 //     carry across the classes of a group in plan order, on the device.
+//   * A spread class with n >= 2 rules (class_spread_rules[c]) runs
+//     vamd_spread_multi_select in place of vamd_spread_select, and its
+//     multi-class revert runs vamd_spread_multi_count_sub before
+//     vamd_spread_revert.  With the column null nothing changes a single
+//     launch.
 //   * An affinity (mode 1) / keyed anti-affinity (mode 2) class always
 //     runs vamd_score_cap -> vamd_domain_mask -> vamd_select_commit (bulk
 //     by size, given sort_scratch) -> vamd_domain_count_add: a launch

@@ -16,7 +16,8 @@ from typing import Optional
 import torch
 
 from .build import LIB_PATH, build
-from .reference import (DEV_MAX_CARDS, NUMA_MAX_ZONES, check_device_request,
+from .reference import (DEV_MAX_CARDS, NUMA_MAX_ZONES, SPREAD_MAX_RULES,
+                        SPREAD_MULTI_LDS_DOMAINS, check_device_request,
                         check_hypernode_table, check_numa_request)
 
 _lib = None
@@ -44,6 +45,17 @@ class VamdJobDesc(Structure):
     ]
 
 
+class VamdSpreadRule(Structure):
+    _fields_ = [("dom_of", c_void_p), ("count", c_void_p),
+                ("D", c_int32), ("skew", c_int32)]
+
+
+class VamdSpreadRules(Structure):
+    """Mirror of ``VamdSpreadRules`` in ``vamd_api.h``, passed by value."""
+    _fields_ = [("r", VamdSpreadRule * SPREAD_MAX_RULES),
+                ("n", c_int32), ("_pad", c_int32)]
+
+
 class VamdCycle(Structure):
     """Mirror of ``VamdCycle`` in ``vamd_api.h`` (same order, same types)."""
     _fields_ = [("struct_size", c_uint64)] + [
@@ -64,7 +76,8 @@ class VamdCycle(Structure):
         ("card_K", c_int32), ("_pad2", c_int32)] + [
         (n, c_void_p) for n in (
             "zone_free", "class_numa_req", "numa_assign")] + [
-        ("zone_Z", c_int32), ("_pad3", c_int32)]
+        ("zone_Z", c_int32), ("_pad3", c_int32),
+        ("class_spread_rules", c_void_p)]
 
 
 def _load():
@@ -97,6 +110,14 @@ def _load():
         raise RuntimeError(
             "the loaded kernel library and this module disagree on "
             "HYPERNODE_LDS_LEAVES; rebuild (python -m volcano_amd.ops.build)")
+    lib.vamd_spread_multi_select.restype = None
+    lib.vamd_spread_multi_count_sub.restype = None
+    lib.vamd_spread_multi_lds_domains.restype = c_int
+    if lib.vamd_spread_multi_lds_domains() != SPREAD_MULTI_LDS_DOMAINS:
+        raise RuntimeError(
+            "the loaded kernel library and this module disagree on "
+            "SPREAD_MULTI_LDS_DOMAINS; rebuild (python -m "
+            "volcano_amd.ops.build)")
     lib.vamd_device_cap.restype = None
     lib.vamd_device_commit.restype = None
     lib.vamd_device_revert.restype = None
@@ -231,6 +252,79 @@ def spread_revert(flag, log_nodes, log_counts, log_len, req, used_t,
         _p(used_t), _p(queue_alloc_row), _p(placed), _p(job_placed),
         _p(dom_of), _p(dom_count), c_int(dom_count.shape[0]),
         c_int(N), c_int(R), _stream())
+
+
+def _spread_rules(op, rules, N) -> VamdSpreadRules:
+    """Layout check of 1..4 ``(dom_of, dom_count, max_skew)`` rules -> the
+    struct the launchers take by value."""
+    rules = list(rules)
+    if not 1 <= len(rules) <= SPREAD_MAX_RULES:
+        raise ValueError(f"{op}: 1 to {SPREAD_MAX_RULES} rules, got "
+                         f"{len(rules)}")
+    out = VamdSpreadRules(n=len(rules))
+    total = 0
+    for k, (dom_of, dom_count, skew) in enumerate(rules):
+        D = dom_count.shape[0]
+        if not 1 <= D <= max(N, 1):
+            raise ValueError(f"{op}: rule {k}: D={D} outside [1, N={N}]")
+        if int(skew) < 1:
+            raise ValueError(f"{op}: rule {k}: max_skew must be >= 1")
+        if dom_of.shape[0] != N:
+            raise ValueError(f"{op}: rule {k}: dom_of must have one entry "
+                             "per node")
+        if dom_of.dtype != torch.int32 or dom_count.dtype != torch.int32 \
+                or not dom_of.is_contiguous() \
+                or not dom_count.is_contiguous():
+            raise ValueError(f"{op}: rule {k}: dom_of and dom_count are "
+                             "contiguous int32")
+        total += D
+        out.r[k] = VamdSpreadRule(_addr(dom_of), _addr(dom_count), D,
+                                  int(skew))
+    if total > SPREAD_MULTI_LDS_DOMAINS:
+        raise ValueError(f"{op}: {total} domains over all rules, at most "
+                         f"{SPREAD_MULTI_LDS_DOMAINS}")
+    return out
+
+
+def spread_multi_select(score, cap, req, ntasks, used_t, queue_alloc_row,
+                        queue_limit_row, log_nodes, log_counts, log_len,
+                        placed, job_placed, rules, fuse_min, scratch=None):
+    """``spread_select`` under 1 to 4 rules ``(dom_of, dom_count, max_skew)``
+    at once: a node is eligible in the intersection of the rules' open
+    domains, every placement joins the counts of every rule.  ``score`` and
+    ``cap`` are consumed; ``scratch`` holds 4*N bytes."""
+    lib = _load()
+    N = score.shape[0]
+    R = req.shape[0]
+    K = log_nodes.shape[0]
+    rs = _spread_rules("spread_multi_select", rules, N)
+    if scratch is None:
+        scratch = spread_scratch(N, score.device)
+    elif scratch.numel() * scratch.element_size() < 4 * N:
+        raise ValueError("spread_multi_select: scratch smaller than 4*N "
+                         "bytes")
+    lib.vamd_spread_multi_select(
+        _p(score), _p(cap), _p(req), c_int(int(ntasks)), _p(used_t),
+        _p(queue_alloc_row), _p(queue_limit_row), _p(log_nodes),
+        _p(log_counts), _p(log_len), _p(placed), _p(job_placed), rs,
+        c_int(int(fuse_min)), _p(scratch), c_int(N), c_int(R), c_int(K),
+        _stream())
+
+
+def spread_multi_count_sub(flag, log_nodes, log_counts, log_len, rules):
+    """When ``flag`` is 0 the logged placements leave the counts of rules
+    1..n-1 — before ``spread_revert``, which handles rule 0 and zeroes the
+    log."""
+    lib = _load()
+    N = rules[0][0].shape[0]
+    K = log_nodes.shape[0]
+    if log_counts.shape[0] != K:
+        raise ValueError("spread_multi_count_sub: log_nodes/log_counts "
+                         "differ in length")
+    rs = _spread_rules("spread_multi_count_sub", rules, N)
+    lib.vamd_spread_multi_count_sub(
+        _p(flag), _p(log_nodes), _p(log_counts), _p(log_len), rs, c_int(N),
+        c_int(K), _stream())
 
 
 def domain_mask(score, cap, dom_of, dom_count, mode, scratch=None):
@@ -504,7 +598,10 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
     a spread class.  An optional ``group_row`` (host int32 numpy [G]) names
     the row of ``dom_of`` each group reads — all network-topology groups
     share one ``leaf_of`` row; without it group g reads row g.  The
-    ``count`` slice of a mode-3 group is its table.
+    ``count`` slice of a mode-3 group is its table.  An optional
+    ``class_rules`` (host int32 numpy [C, 9]: n, then four (group, maxSkew)
+    pairs) names every rule of the spread classes that have several (n >= 2;
+    rule 0 is also the class's ``class_group``/``class_skew``).
 
     ``devices`` (plans with device-request classes only) is a dict: the
     card planes ``mem_used``/``cores_used``/``state`` device i32 [K, N],
@@ -554,6 +651,35 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
                     rows.shape[0] != spread["domains"].shape[0]:
                 raise ValueError("run_cycle: group_row must be int32 [G]")
             cy.group_row = rows.ctypes.data
+        cr = spread.get("class_rules")
+        if cr is not None:
+            doms = spread["domains"]
+            if cr.shape != (n_classes, 9) or cr.dtype != "int32" \
+                    or not cr.flags["C_CONTIGUOUS"]:
+                raise ValueError("run_cycle: class_rules must be int32 "
+                                 "[C, 9]")
+            # the slice of a group that a mode-3 class names is a table
+            tables = set() if mode is None else \
+                set(spread["class_group"][mode == 3].tolist())
+            for c, row in enumerate(cr):
+                n = int(row[0])
+                if n < 2:
+                    continue
+                gs, skews = row[1:1 + 2 * n:2], row[2:2 + 2 * n:2]
+                if n > SPREAD_MAX_RULES or gs.min() < 0 \
+                        or gs.max() >= doms.shape[0] or skews.min() < 1 \
+                        or gs[0] != spread["class_group"][c] \
+                        or (mode is not None and mode[c] != 0) \
+                        or len(set(gs.tolist())) != n \
+                        or tables & set(gs.tolist()) \
+                        or int(doms[gs].sum()) > SPREAD_MULTI_LDS_DOMAINS:
+                    raise ValueError(f"run_cycle: class_rules row {c}: 2 to "
+                                     f"{SPREAD_MAX_RULES} distinct spread "
+                                     "groups, maxSkew >= 1, rule 0 = "
+                                     "class_group with mode 0, at most "
+                                     f"{SPREAD_MULTI_LDS_DOMAINS} domains in "
+                                     "all")
+            cy.class_spread_rules = cr.ctypes.data
     if devices is not None:
         K, _ = _unit_planes("run_cycle", _CARDS, (
             devices["mem_used"], devices["cores_used"], devices["state"]),

@@ -316,6 +316,115 @@ def spread_revert(
                 queue_alloc, placed, job_placed)
 
 
+SPREAD_MAX_RULES = 4            # rules of one spread_multi_select_commit
+# largest sum of D over them on the device (``SM_LDS_DOMAINS`` of
+# scheduler_kernels.hip: 32 KB of eligibility bits; checked on load)
+SPREAD_MULTI_LDS_DOMAINS = 1 << 18
+
+
+def spread_multi_select_commit(
+    score: torch.Tensor, cap: torch.Tensor, req: torch.Tensor, ntasks: int,
+    used: torch.Tensor, queue_alloc: torch.Tensor, queue_limit: torch.Tensor,
+    log_nodes: torch.Tensor, log_counts: torch.Tensor, log_len: torch.Tensor,
+    placed: torch.Tensor, job_placed: torch.Tensor,
+    rules,                      # 1..4 x (dom_of [N] i32, dom_count [D_r] i32
+                                #         in place, max_skew >= 1)
+) -> None:
+    """``spread_select_commit`` under several topology-spread constraints
+    at once (zone AND hostname): node ``n`` may take an instance only
+    while, for EVERY rule ``r``, ``dom_r[n] >= 0`` and
+    ``cnt_r[dom_r[n]] + 1 - min(cnt_r) <= skew_r`` — each minimum over all
+    ``D_r`` domains of its rule.  A placement joins the node's domain in
+    every rule.  Everything else (queue budget, log, ``used``, the stop at
+    the first state without an eligible node) is ``spread_select_commit``,
+    which this equals with one rule.
+
+    A plain sequential loop — the source of truth of the HIP
+    ``spread_multi_select_kernel``."""
+    rules = list(rules)
+    if not 1 <= len(rules) <= SPREAD_MAX_RULES:
+        raise ValueError(f"1 to {SPREAD_MAX_RULES} spread rules per class")
+    if any(int(skew) < 1 for _, _, skew in rules):
+        raise ValueError("max_skew must be >= 1")
+    N = score.shape[0]
+    log_nodes.zero_()
+    log_counts.zero_()
+
+    headroom = queue_limit - queue_alloc
+    pos = req > EPS
+    per_dim = torch.where(pos, (headroom + EPS) / torch.clamp(req, min=EPS),
+                          torch.full_like(headroom, float(BIG_CAP)))
+    quota = int(per_dim.amin().clamp(min=0, max=float(BIG_CAP)).floor())
+    budget = min(int(ntasks), quota)
+
+    sc = score.tolist()
+    doms = [d.tolist() for d, _, _ in rules]
+    cnts = [c.tolist() for _, c, _ in rules]
+    skews = [int(s) for _, _, s in rules]
+    rem = [int(c) if s > NEG_INF and all(d[n] >= 0 for d in doms) else 0
+           for n, (s, c) in enumerate(zip(sc, cap.tolist()))]
+    slot = {}                   # node → log entry
+    nodes: list = []
+    counts: list = []
+    total = 0
+    while total < budget:
+        lows = [min(c) for c in cnts]
+        best = -1
+        for n in range(N):
+            if rem[n] > 0 and (best < 0 or sc[n] > sc[best]) and all(
+                    c[d[n]] + 1 - m <= k
+                    for c, d, m, k in zip(cnts, doms, lows, skews)):
+                best = n
+        if best < 0:
+            break
+        rem[best] -= 1
+        for c, d in zip(cnts, doms):
+            c[d[best]] += 1
+        total += 1
+        e = slot.get(best)
+        if e is None:
+            slot[best] = len(nodes)
+            nodes.append(best)
+            counts.append(1)
+        else:
+            counts[e] += 1
+
+    m = len(nodes)
+    assert m <= log_nodes.shape[0], "undo-log slot too small"
+    dev = score.device
+    idx = torch.tensor(nodes, dtype=torch.long, device=dev)
+    c32 = torch.tensor(counts, dtype=torch.int32, device=dev)
+    log_nodes[:m] = idx.to(torch.int32)
+    log_counts[:m] = c32
+    log_len.fill_(m)
+    for (_, dom_count, _), c in zip(rules, cnts):
+        dom_count.copy_(torch.tensor(c, dtype=torch.int32, device=dev))
+    used.index_add_(0, idx, c32.to(torch.float32).unsqueeze(1)
+                    * req.unsqueeze(0))
+    queue_alloc += torch.tensor(float(total), device=dev) * req
+    placed.fill_(total)
+    job_placed.add_(total)
+
+
+def spread_multi_revert(
+    flag: torch.Tensor, log_nodes: torch.Tensor, log_counts: torch.Tensor,
+    log_len: torch.Tensor, req: torch.Tensor, used: torch.Tensor,
+    queue_alloc: torch.Tensor, placed: torch.Tensor,
+    job_placed: torch.Tensor,
+    rules,                      # as in spread_multi_select_commit
+) -> None:
+    """``cond_revert`` for a class with several spread rules: the logged
+    placements go back to the counts of every rule first."""
+    if int(flag) == 0:
+        n = int(log_len)
+        nodes = log_nodes[:n].to(torch.long)
+        for dom_of, dom_count, _ in rules:
+            dom_count.index_add_(0, dom_of[nodes].to(torch.long),
+                                 -log_counts[:n])
+    cond_revert(flag, log_nodes, log_counts, log_len, req, used,
+                queue_alloc, placed, job_placed)
+
+
 AFFINITY = 1                    # domain-rule modes of affinity_select_commit
 ANTI_AFFINITY = 2
 

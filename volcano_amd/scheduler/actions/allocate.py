@@ -657,18 +657,31 @@ class _ExactRules:
                 self._leaf_row, ref_ops.hypernode_table(
                     tiers, max(1, int(need)), hx.n_leaves, pin, soft))
         elif dom is not None:
-            kind, (g, arg) = dom      # arg: maxSkew (spread), mode (affinity)
+            kind, rule = dom
             pub = self.spread if kind == "spread" else self.affinity
-            pg = self._group_of.get((kind, g))
-            if pg is None:
-                pg = self._group_of[kind, g] = plan.add_spread_group(
-                    pub.dom_of[g], pub.count[g])
-            if kind == "spread":
-                cp.spread = (pg, arg)
+
+            def group(g):
+                pg = self._group_of.get((kind, g))
+                if pg is None:
+                    pg = self._group_of[kind, g] = plan.add_spread_group(
+                        pub.dom_of[g], pub.count[g])
+                return pg
+
+            if isinstance(rule, list):
+                # several spread constraints: every group joins the plan and
+                # every rule loses its saturation bit
+                cp.spread_rules = [(group(g), skew) for g, skew in rule]
+                cp.spread = cp.spread_rules[0]
+                for g, _ in rule:
+                    _clear_bit(cp, "forbid", pub.sat_bit[g])
+            elif kind == "spread":
+                g, skew = rule
+                cp.spread = (group(g), skew)
                 _clear_bit(cp, "forbid", pub.sat_bit[g])    # saturated zones
             else:
-                cp.affinity = (pg, arg)     # hosting set / occupied domains
-                _clear_bit(cp, "require" if arg == ref_ops.AFFINITY
+                g, mode = rule
+                cp.affinity = (group(g), mode)  # hosting set / occupied domains
+                _clear_bit(cp, "require" if mode == ref_ops.AFFINITY
                            else "forbid", pub.open_bit[g])
         if dv is not None:
             if plan.device_state is None:

@@ -118,6 +118,12 @@ class ClassPlan:
     # placed by the per-placement topology-spread select instead of
     # select_commit.  Never combined with ``bundle``.
     spread: Optional[Tuple[int, int]] = None
+    # every (group, maxSkew) of a class under SEVERAL spread constraints
+    # (zone and hostname, ...), 2 to ref.SPREAD_MAX_RULES of them over
+    # distinct groups; ``spread`` is then rule 0.  Placed by the multi-rule
+    # spread select, which holds every maxSkew before every placement.
+    # Never combined with ``bundle``, ``affinity`` or ``hypernode``.
+    spread_rules: Optional[List[Tuple[int, int]]] = None
     # (index into CyclePlan.spread_groups, mode): inter-pod affinity
     # (mode 1) or keyed anti-affinity (mode 2) enforced per placement over
     # the group's domains — domain mask + select_commit + count update.
@@ -393,6 +399,38 @@ class CyclePlan:
             min_available=cp.min_needed))
         self.classes.append(cp)
 
+    def check_spread_rules(self, c: int, cp: ClassPlan) -> None:
+        """``cp.spread_rules`` of class ``c`` against the plan's groups (part
+        of ``finalize``; whoever sets the rules on a finalized plan runs it
+        itself)."""
+        if cp.spread_rules is None:
+            return
+        rules = [tuple(r) for r in cp.spread_rules]
+        gs = [g for g, _ in rules]
+        if not 1 <= len(rules) <= ref.SPREAD_MAX_RULES or \
+                cp.spread is None or tuple(cp.spread) != rules[0]:
+            raise ValueError(
+                f"class {c}: 1 to {ref.SPREAD_MAX_RULES} spread rules, the "
+                "first of them in ``spread``")
+        if any(not 0 <= g < len(self.spread_groups) for g in gs):
+            raise ValueError(f"class {c}: unknown spread group")
+        if len(set(gs)) != len(gs):
+            raise ValueError(f"class {c}: two spread rules over one group")
+        if any(skew < 1 for _, skew in rules):
+            raise ValueError(f"class {c}: maxSkew must be >= 1")
+        if any(self.spread_groups[g].row >= 0 for g in gs):
+            raise ValueError(f"class {c}: a spread rule names a hypernode "
+                             "group")
+        if sum(self.spread_groups[g].count.shape[0] for g in gs) \
+                > ref.SPREAD_MULTI_LDS_DOMAINS:
+            raise ValueError(
+                f"class {c}: its spread rules have more than "
+                f"{ref.SPREAD_MULTI_LDS_DOMAINS} domains in all")
+        if cp.bundle is not None or cp.affinity is not None \
+                or cp.hypernode is not None:
+            raise ValueError(f"class {c}: several spread rules never "
+                             "combine with bundle, affinity or hypernode")
+
     def finalize(self) -> None:
         """Assign undo-log slots (one contiguous region per class),
         normalize constraint widths (the label-bit registry may have
@@ -439,6 +477,7 @@ class CyclePlan:
                 if cp.bundle is not None:
                     raise ValueError(f"class {c}: spread classes never "
                                      "bundle")
+            self.check_spread_rules(c, cp)
             if cp.affinity is not None:
                 g, mode = cp.affinity
                 if not 0 <= g < len(self.spread_groups):
@@ -545,7 +584,13 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
         if cp.device is not None:
             ref.device_revert(flag, log_nodes[sl], log_len[c], *cards,
                               dev_assign[sl], cp.device)
-        if cp.spread is not None or cp.affinity is not None:
+        if cp.spread_rules is not None and len(cp.spread_rules) >= 2:
+            ref.spread_multi_revert(
+                flag, log_nodes[sl], log_counts[sl], log_len[c], req, used,
+                plan.queue_alloc[cp.queue_idx], class_placed[c],
+                job_placed[j],
+                [(sp_dom[g], sp_cnt[g], k) for g, k in cp.spread_rules])
+        elif cp.spread is not None or cp.affinity is not None:
             g = (cp.spread or cp.affinity)[0]
             ref.spread_revert(flag, log_nodes[sl], log_counts[sl],
                               log_len[c], req, used,
@@ -584,7 +629,15 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
                 # u + c*r - c*r is not u in f32 once usage comes in bytes
                 used_before = used.clone()
                 qa_before = plan.queue_alloc[cp.queue_idx].clone()
-            if cp.spread is not None:
+            if cp.spread_rules is not None and len(cp.spread_rules) >= 2:
+                ref.spread_multi_select_commit(
+                    score, cap, req, cp.ntasks, used,
+                    plan.queue_alloc[cp.queue_idx],
+                    plan.queue_limit[cp.queue_idx],
+                    log_nodes[sl], log_counts[sl], log_len[c],
+                    class_placed[c], job_placed[j],
+                    [(sp_dom[g], sp_cnt[g], k) for g, k in cp.spread_rules])
+            elif cp.spread is not None:
                 g, skew = cp.spread
                 ref.spread_select_commit(
                     score, cap, req, cp.ntasks, used,
@@ -792,6 +845,17 @@ def run_plan_hip(plan: CyclePlan) -> CycleResult:
             spread["class_mode"] = cm
         if row_of_leafmap:
             spread["group_row"] = grow
+        # classes under several spread rules: n, then the (group, maxSkew)
+        # pairs; the column exists only when the plan has such a class
+        if any(cp.spread_rules is not None and len(cp.spread_rules) >= 2
+               for cp in plan.classes):
+            cr = np.zeros((C, 9), dtype=np.int32)
+            for c, cp in enumerate(plan.classes):
+                if cp.spread_rules is not None and len(cp.spread_rules) >= 2:
+                    cr[c, 0] = len(cp.spread_rules)
+                    cr[c, 1:1 + 2 * len(cp.spread_rules)] = \
+                        np.asarray(cp.spread_rules, dtype=np.int32).ravel()
+            spread["class_rules"] = cr
         plan.spread_counts = [count[int(o):int(o) + int(d)]
                               for o, d in zip(offs, lens)]
 

@@ -5,7 +5,11 @@ Simplified hard semantics: pods declaring
 ``affinity = {"topologySpread": {"group": G, "topologyKey": K,
 "maxSkew": s}}`` must spread across the values of node label K so that
 no value's member count exceeds the minimum count by more than
-``maxSkew``.
+``maxSkew``.  ``topologySpread`` may also be a list of such dicts — zone
+``maxSkew: 1`` together with ``kubernetes.io/hostname`` ``maxSkew: 1`` is
+the textbook pair: every entry must hold, a member counts in every
+``(group, topologyKey)`` it names, and a node that lacks the label of any
+entry is out of bounds.
 
 Mapping: at session open the plugin counts placed members of G per
 topology value and forbids (dynamic bit) the nodes of every value that
@@ -31,6 +35,13 @@ the session-open saturation bit (unlabeled nodes stay forbidden);
 backfill, preempt, reclaim and the nominated fast path keep the
 cycle-granular bit.
 
+A class with a list of 2 to 4 entries resolves to all its rules,
+``[(group, maxSkew), ...]``, and is placed by the multi-rule select
+(``spread_multi_select_commit`` / ``spread_multi_select_kernel``), which
+holds every ``maxSkew`` before every placement.  A list longer than 4, or
+one whose rules have more than ``SPREAD_MULTI_LDS_DOMAINS`` domains in all,
+keeps the cycle-granular bits for that class (logged once).
+
 ``exact`` is ignored — the cycle-granular path above is used — for jobs
 with a SubGroupPolicy and for runs under the soft-shard coordinator:
 both can drop placements after the kernel has counted them.
@@ -39,11 +50,13 @@ both can drop placements after the kernel has counted them.
 from __future__ import annotations
 
 from collections import defaultdict
+import logging
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
 from ...api.types import TaskStatus
+from ...ops.reference import SPREAD_MAX_RULES, SPREAD_MULTI_LDS_DOMAINS
 from ..tensors import set_plane_bit
 from .base import Plugin, register
 
@@ -51,13 +64,33 @@ OCCUPY = (TaskStatus.ALLOCATED, TaskStatus.BINDING, TaskStatus.BOUND,
           TaskStatus.RUNNING)
 
 
-def _spec(pod):
+log = logging.getLogger(__name__)
+# classes already reported as cycle-granular.  Per process on purpose: the
+# plugin and what it publishes are rebuilt at every session open, so state
+# kept on either would repeat the line every cycle.
+_LOGGED: set = set()
+
+
+def _specs(pod) -> list:
+    """The pod's spread constraints: ``topologySpread`` is one dict or a
+    list of them; one entry per (group, topologyKey), the first wins."""
     aff = pod.affinity if pod is not None else None
-    if isinstance(aff, dict):
-        s = aff.get("topologySpread")
-        if isinstance(s, dict) and s.get("group") and s.get("topologyKey"):
-            return s
-    return None
+    s = aff.get("topologySpread") if isinstance(aff, dict) else None
+    out, seen = [], set()
+    for e in (s if isinstance(s, (list, tuple)) else (s,)):
+        if isinstance(e, dict) and e.get("group") and e.get("topologyKey") \
+                and (e["group"], e["topologyKey"]) not in seen:
+            seen.add((e["group"], e["topologyKey"]))
+            out.append(e)
+    return out
+
+
+def _log_once(specs, why: str) -> None:
+    key = tuple((e["group"], e["topologyKey"]) for e in specs)
+    if key not in _LOGGED:
+        _LOGGED.add(key)
+        log.warning("topologyspread: %s for %s; the class keeps the "
+                    "cycle-granular path", why, list(key))
 
 
 def _truthy(v) -> bool:
@@ -84,22 +117,34 @@ class SpreadExact:
         self.count.append(count)
         self.sat_bit.append(sat_bit)
 
-    def resolve_task(self, task) -> Optional[Tuple[int, int]]:
-        """(group index, maxSkew >= 1) of a task's class, or None."""
+    def resolve_task(self, task):
+        """(group index, maxSkew >= 1) of a task's class; with several
+        constraints the list of all of them; None when there is none or
+        the class stays cycle-granular."""
         sig = task.class_signature()
         got = self._memo.get(sig, self)
         if got is not self:
             return got
         out = None
-        s = _spec(task.pod)
-        if s is not None:
-            g = self._index.get((s["group"], s["topologyKey"]))
-            if g is not None:
-                out = (g, max(1, int(s.get("maxSkew", 1))))
+        specs = _specs(task.pod)
+        gs = [self._index.get((s["group"], s["topologyKey"])) for s in specs]
+        if specs and None not in gs:
+            rules = [(g, max(1, int(s.get("maxSkew", 1))))
+                     for g, s in zip(gs, specs)]
+            if len(rules) == 1:
+                out = rules[0]
+            elif len(rules) > SPREAD_MAX_RULES:
+                _log_once(specs, f"more than {SPREAD_MAX_RULES} constraints")
+            elif sum(len(self.count[g]) for g in gs) \
+                    > SPREAD_MULTI_LDS_DOMAINS:
+                _log_once(specs, f"more than {SPREAD_MULTI_LDS_DOMAINS} "
+                                 "domains in all")
+            else:
+                out = rules
         self._memo[sig] = out
         return out
 
-    def resolve(self, tclass, job=None) -> Optional[Tuple[int, int]]:
+    def resolve(self, tclass, job=None):
         return self.resolve_task(tclass.tasks[0])
 
 
@@ -115,16 +160,14 @@ class TopologySpreadPlugin(Plugin):
         specs: Dict[tuple, dict] = {}
         for job in ssn.jobs.values():
             for t in job.tasks.values():
-                s = _spec(t.pod)
-                if s is None:
-                    continue
-                gk = (s["group"], s["topologyKey"])
-                specs[gk] = s
-                if t.status in OCCUPY and t.node_name in ssn.nodes:
-                    ni = ssn.nodes[t.node_name]
-                    val = ni.node.meta.labels.get(s["topologyKey"])
-                    if val is not None:
-                        counts[gk][val] += 1
+                for s in _specs(t.pod):
+                    gk = (s["group"], s["topologyKey"])
+                    specs[gk] = s
+                    if t.status in OCCUPY and t.node_name in ssn.nodes:
+                        ni = ssn.nodes[t.node_name]
+                        val = ni.node.meta.labels.get(s["topologyKey"])
+                        if val is not None:
+                            counts[gk][val] += 1
         if not specs:
             return
 
@@ -178,13 +221,11 @@ class TopologySpreadPlugin(Plugin):
             published.add(gk, dom_of, count, bits.get(gk))
 
         def hook(tclass, job, require, forbid):
-            s = _spec(tclass.tasks[0].pod)
-            if s is None:
-                return
-            gk = (s["group"], s["topologyKey"])
-            for bit in (bits.get(gk), unl_bits.get(gk)):
-                if bit is not None:
-                    set_plane_bit(forbid, bit)
+            for s in _specs(tclass.tasks[0].pod):
+                gk = (s["group"], s["topologyKey"])
+                for bit in (bits.get(gk), unl_bits.get(gk)):
+                    if bit is not None:
+                        set_plane_bit(forbid, bit)
 
         ssn.class_constraint_hooks.append(hook)
         if published is not None and published.keys:
