@@ -83,6 +83,15 @@ def build(force: bool = False, verbose: bool = True) -> Path:
     if force or needs_build_hip():
         cmd = [
             HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17",
+            # No packed-f32 arithmetic (v_pk_fma_f32 / v_pk_mul_f32) in the
+            # device code: the score body, inlined into many kernels, is
+            # then scalar FMAs and multiplies in each.  Where a*b+c is
+            # contracted is still the compiler's choice per inlining
+            # context (docs/kernels.md, known limits).  A cc1 switch, because
+            # the driver has no option for it and forwards none of this kind
+            # to the device side alone: the host pass prints that it ignores
+            # the feature.
+            "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
             "-fPIC", "-shared", "-o", str(LIB_PATH),
         ] + [str(CSRC / s) for s in SOURCES]
         if verbose:

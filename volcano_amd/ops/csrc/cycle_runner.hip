@@ -12,6 +12,8 @@
 
 #include "vamd_api.h"
 
+#include <atomic>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
@@ -111,6 +113,8 @@ struct ClassView {
     // every rule of a spread class that has several (multi.n >= 2, rule 0
     // being the one above); n == 0 otherwise
     VamdSpreadRules multi;
+    // the chosen node is scored again after every placement
+    bool rescore;
 };
 
 struct Runner {
@@ -119,6 +123,7 @@ struct Runner {
     const bool domains_live;
     const bool devices_live;
     const bool numa_live;
+    const bool rescore_live;
 
     Runner(const VamdCycle& c, hipStream_t s)
         : cy(c), stream(s),
@@ -131,7 +136,9 @@ struct Runner {
                        c.class_dev_req != nullptr &&
                        c.dev_assign != nullptr && c.card_K >= 1),
           numa_live(c.zone_free != nullptr && c.class_numa_req != nullptr &&
-                    c.numa_assign != nullptr && c.zone_Z >= 1) {}
+                    c.numa_assign != nullptr && c.zone_Z >= 1),
+          rescore_live(c.class_rescore != nullptr &&
+                       c.rescore_slot != nullptr) {}
 
     int group_of(int c) const { return domains_live ? cy.class_group[c] : -1; }
 
@@ -147,6 +154,11 @@ struct Runner {
         if (!numa_live) return nullptr;
         const int32_t* rq = cy.class_numa_req + (size_t)c * 2;
         return rq[1] != 0 ? rq : nullptr;
+    }
+
+    // re-scored after every placement: the split path only
+    bool rescore_of(int c) const {
+        return rescore_live && cy.class_rescore[c] != 0;
     }
 
     // packed per card or per zone: the split path only
@@ -169,7 +181,8 @@ struct Runner {
             cy.log_nodes + cd.log_off, cy.log_counts + cd.log_off,
             cy.log_len + c, cy.class_placed + c, cy.job_placed + j,
             cy.job_flag + j, single ? gang_fuse_min(job, cd) : -1,
-            g, 0, 0, 0, nullptr, nullptr, dev_of(c), numa_of(c), {}};
+            g, 0, 0, 0, nullptr, nullptr, dev_of(c), numa_of(c), {},
+            rescore_of(c)};
         if (g >= 0) {
             v.mode = cy.class_mode != nullptr ? cy.class_mode[c] : 0;
             if (v.mode == 0) v.skew = cy.class_skew[c];
@@ -218,6 +231,17 @@ struct Runner {
             cy.cap_scratch, v.cd.ntasks, v.queue_alloc, v.queue_limit,
             v.log_nodes, v.log_counts, v.log_len, v.placed, v.job_placed,
             v.fuse_min, cy.N, cy.R, cy.W, v.cd.log_cap, stream);
+    }
+
+    void rescore_select(const ClassView& v) const {
+        vamd_rescore_select(
+            cy.alloc, cy.used, v.pl.ext, cy.ready, cy.taints, cy.planes,
+            v.req, v.tol, v.require, v.forbid, v.cd.w_least, v.cd.w_most,
+            v.cd.w_bal, cy.dim_w, v.pl.bias, cy.score_scratch,
+            cy.cap_scratch, v.cd.ntasks, v.queue_alloc, v.queue_limit,
+            v.log_nodes, v.log_counts, v.log_len, v.placed, v.job_placed,
+            v.fuse_min, cy.rescore_slot, cy.N, cy.R, cy.W, v.cd.log_cap,
+            stream);
     }
 
     void spread_select(const ClassView& v) const {
@@ -316,7 +340,7 @@ struct Runner {
     // (and count update).
     void run_class(const ClassView& v) const {
         if (v.group < 0 && v.dev == nullptr && v.numa == nullptr &&
-                v.cd.ntasks < BULK_TASKS && cy.N <= 4096) {
+                !v.rescore && v.cd.ntasks < BULK_TASKS && cy.N <= 4096) {
             // small class on a small inventory, no rule and no request: ONE
             // fused launch (score in-block + select).  At larger N the
             // one-block score loses the multi-CU latency hiding of the
@@ -333,6 +357,13 @@ struct Runner {
             // placement, so always the spread select, whatever the class
             // size; with several rules the node-scan select that intersects
             // them
+            if (v.rescore) {
+                static std::atomic_flag said = ATOMIC_FLAG_INIT;
+                if (!said.test_and_set())
+                    fprintf(stderr, "vamd: a topology-spread class keeps "
+                            "static scores within the class; its re-score "
+                            "flag is ignored\n");
+            }
             if (v.multi.n >= 2) spread_multi_select(v);
             else spread_select(v);
         } else {
@@ -341,8 +372,11 @@ struct Runner {
             // group's live counts, or confining the class to the one
             // hypernode chosen from the live cap), then the ordinary select
             // (bulk by size) — a launch count constant in ntasks
+            // A re-scoring class takes the select that scores the chosen
+            // node again after every placement, behind the same mask.
             if (v.group >= 0) domain_mask(v);
-            select(v);
+            if (v.rescore) rescore_select(v);
+            else select(v);
             // a hypernode group's slice is a read-only table: no count
             // update follows
             if (v.group >= 0 && v.mode != MODE_HYPERNODE)
@@ -367,13 +401,13 @@ struct Runner {
             revert(view(j, c));
     }
 
-    // a single-class small job without a domain rule, device or NUMA request;
-    // anything else breaks a chain run
+    // a single-class small job without a domain rule, device or NUMA request
+    // or re-scoring; anything else breaks a chain run
     bool chainable(int j) const {
         const VamdJobDesc& jb = cy.jobs[j];
         return jb.class_end - jb.class_begin == 1 &&
             group_of(jb.class_begin) < 0 &&
-            !packed(jb.class_begin) &&
+            !packed(jb.class_begin) && !rescore_of(jb.class_begin) &&
             cy.classes[jb.class_begin].ntasks < BULK_TASKS;
     }
 
@@ -388,14 +422,15 @@ struct Runner {
         return e;
     }
 
-    // The megacycle kernel has no bulk, no domain-rule select and no card or
-    // zone planes: such a plan runs per class.  False as well when the
-    // staging allocation fails: fall through to per-class launches.
+    // The megacycle kernel has no bulk, no domain-rule select, no card or
+    // zone planes and no re-scoring: such a plan runs per class.  False as
+    // well when the staging allocation fails: fall through to per-class
+    // launches.
     bool try_megacycle() const {
         if (cy.n_classes < 32) return false;
         for (int c = 0; c < cy.n_classes; ++c)
             if (cy.classes[c].ntasks >= BULK_TASKS || group_of(c) >= 0 ||
-                    packed(c))
+                    packed(c) || rescore_of(c))
                 return false;
         void* blob;
         VamdDevDescs dd;

@@ -43,6 +43,20 @@ constexpr long long BIG_CAP = 1 << 30;
 // exactness contract with the torch oracle).
 struct NodeScore { float s; int cap; };
 
+DEVINL float acc_add(float acc, int count, float req);
+
+// usage of one (dim, node) with k instances of the class staged on the node:
+// the value dev_commit_log writes for a count of k (ONE rounding, never k
+// accumulated adds).  k is a literal 0 everywhere but in the re-scoring
+// select, where the branch folds away.  That select also passes
+// STATIC = false: readiness, taints and label planes do not move with usage
+// and the node it scores again has passed them, so they are not read again.
+DEVINL float staged_used(const float* __restrict__ used, size_t off, int k,
+                         float rq) {
+    return k ? acc_add(used[off], k, rq) : used[off];
+}
+
+template <bool STATIC = true>
 DEVINL NodeScore node_score_one(
     int i,
     const float* __restrict__ alloc,
@@ -58,14 +72,18 @@ DEVINL NodeScore node_score_one(
     float w_least, float w_most, float w_bal,
     const float* __restrict__ dim_w, float wsum,
     const float* __restrict__ bias,
-    int N, int R, int W)
+    int N, int R, int W,
+    int k = 0)      // instances of this class staged on node i (re-score)
 {
-    bool feasible = ready[i] != 0;
-    feasible = feasible && ((taints[i] & ~tolerated) == 0);
-    for (int w = 0; w < W; ++w) {
-        int64_t p = planes[(size_t)w * N + i];
-        feasible = feasible && ((p & require[w]) == require[w]);
-        feasible = feasible && ((p & forbid[w]) == 0);
+    bool feasible = true;
+    if (STATIC) {
+        feasible = ready[i] != 0;
+        feasible = feasible && ((taints[i] & ~tolerated) == 0);
+        for (int w = 0; w < W; ++w) {
+            int64_t p = planes[(size_t)w * N + i];
+            feasible = feasible && ((p & require[w]) == require[w]);
+            feasible = feasible && ((p & forbid[w]) == 0);
+        }
     }
 
     long long cap = BIG_CAP;
@@ -73,10 +91,10 @@ DEVINL NodeScore node_score_one(
     for (int r = 0; r < R; ++r) {
         size_t off = (size_t)r * N + i;
         float a = alloc[off];
-        float u = used[off];
+        float rq = req[r];
+        float u = staged_used(used, off, k, rq);
         float e = extra ? extra[off] : 0.f;
         float avail = a - u + e;
-        float rq = req[r];
         // the fit test covers EVERY dim, as in the oracle: a node over-
         // committed (used > alloc) in a dim the class does not request
         // is still not a place to put more work
@@ -104,7 +122,7 @@ DEVINL NodeScore node_score_one(
         float var = 0.f;
         for (int r = 0; r < R; ++r) {
             size_t off = (size_t)r * N + i;
-            float f = fminf((used[off] + req[r]) /
+            float f = fminf((staged_used(used, off, k, req[r]) + req[r]) /
                             fmaxf(alloc[off], EPS), 1.0f);
             float d = f - mean;
             var += d * d;
@@ -978,6 +996,199 @@ __global__ void spread_revert_kernel(
     __syncthreads();
     dev_cond_revert(flag, log_nodes, log_counts, log_len, req, used,
                     queue_alloc, placed, job_placed, N, R);
+}
+
+// ---------------------------------------------------------------------------
+// K2 select that RE-SCORES the chosen node after every placement (nodeorder
+// exact) — oracle: reference.py rescore_select_commit.  The static selects
+// fill a node to capacity at the score it had when the class started; here a
+// node that took an instance is scored again on its staged usage before the
+// next instance is placed, as the reference's per-task scoring does, so a
+// least-requested class spreads and a most-requested class still packs.
+// Only the winner's score moves, which is what keeps this cheap:
+//
+//   * keys are spread_key(score, i): one unsigned max is score-descending,
+//     index-ascending.  0 = no node.
+//   * every thread caches the best AND the second-best key of its 1024-
+//     stride slice; the block reduce carries the pair (wave shuffles, then
+//     the 16 wave pairs through LDS) and merges two pairs into the top two
+//     of the four.  Each round so knows the winner b and `runner`, the best
+//     key among ALL other nodes — which may live in b's own slice, hence
+//     out of the reduce and not out of a second pass.
+//   * run-length placement: thread 0 keeps placing on b without another
+//     reduce while b has capacity, the budget lasts and
+//     spread_key(new score, b) > runner (the tie rule comes for free: on
+//     an equal score the lower index has the larger key).  Each step is
+//     k++ and one node_score_one(b, k) in registers — the body
+//     score_cap_kernel runs, on used_k = fma(k, req, used), so the bits are
+//     those score_cap would produce on a plane holding used_k.  A class
+//     whose score does not fall with usage costs one reduce per NODE, like
+//     the static select; a least-requested class about one per instance.
+//   * slot[n] maps a node to its log entry (-1: none) and log_counts[slot]
+//     is its staged count k: a node that wins again later resumes there.
+//   * after the run b's owner reads the new score[b] and rescans its slice
+//     for its top two (O(N/1024), L2-resident).
+//
+// Barrier conventions of dev_select_commit: thread 0 owns the remaining,
+// cursor and log counters and publishes go with the winner; loop exits are
+// read block-uniformly after a barrier; no barrier under divergent control
+// flow.  The loop never writes `used` (log-first): a gang that misses
+// fuse_min is discarded by not calling dev_commit_log.
+// ---------------------------------------------------------------------------
+struct Top2 { unsigned long long k1, k2; };
+
+// keys of distinct nodes differ (the index is in the low half), so only the
+// empty key 0 can repeat
+DEVINL Top2 top2_offer(Top2 t, unsigned long long k) {
+    if (k > t.k1) { t.k2 = t.k1; t.k1 = k; }
+    else if (k > t.k2) t.k2 = k;
+    return t;
+}
+
+DEVINL Top2 top2_merge(Top2 a, Top2 b) {
+    Top2 o;
+    if (a.k1 >= b.k1) { o.k1 = a.k1; o.k2 = a.k2 > b.k1 ? a.k2 : b.k1; }
+    else { o.k1 = b.k1; o.k2 = b.k2 > a.k1 ? b.k2 : a.k1; }
+    return o;
+}
+
+DEVINL Top2 top2_reduce(Top2 x, int width) {
+    for (int off = width / 2; off > 0; off >>= 1) {
+        Top2 o;
+        o.k1 = __shfl_down(x.k1, off);
+        o.k2 = __shfl_down(x.k2, off);
+        x = top2_merge(x, o);
+    }
+    return x;
+}
+
+__global__ void __launch_bounds__(SC_THREADS)
+rescore_select_kernel(
+    const float* __restrict__ alloc, float* __restrict__ used,
+    const float* __restrict__ extra, const float* __restrict__ req,
+    float w_least, float w_most, float w_bal,
+    const float* __restrict__ dim_w, const float* __restrict__ bias,
+    float* __restrict__ score,        // [N] consumed: holds the live scores
+    const int* __restrict__ cap,      // [N]
+    int ntasks,
+    float* __restrict__ queue_alloc, const float* __restrict__ queue_limit,
+    int* __restrict__ log_nodes, int* __restrict__ log_counts,
+    int* __restrict__ log_len, int* __restrict__ placed,
+    int* __restrict__ job_placed, int fuse_min,
+    int* __restrict__ slot,           // [N] scratch: node -> log entry
+    int N, int R, int K)
+{
+    __shared__ unsigned long long s_w1[SC_WAVES];
+    __shared__ unsigned long long s_w2[SC_WAVES];
+    __shared__ unsigned long long s_best;
+    __shared__ unsigned long long s_runner;
+    __shared__ int s_budget;
+    __shared__ int s_remaining;
+    __shared__ int s_cursor;
+    __shared__ int s_go;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wid = tid / WAVE;
+
+    if (tid == 0) {
+        long long b = dev_queue_budget(req, queue_limit, queue_alloc, ntasks,
+                                       R);
+        s_budget = (int)min(max(b, 0ll), (long long)INT32_MAX);
+        s_remaining = s_budget;
+        s_cursor = 0;
+    }
+    float wsum = 0.f;
+    for (int r = 0; r < R; ++r) wsum += dim_w[r];
+    wsum = fmaxf(wsum, EPS);
+
+    // nodes that can never take an instance leave the score vector; the
+    // others enter their owner's top two
+    Top2 loc = {0ull, 0ull};
+    for (int i = tid; i < N; i += SC_THREADS) {
+        slot[i] = -1;
+        float s = score[i];
+        if (s > NEG_INF && cap[i] > 0) loc = top2_offer(loc, spread_key(s, i));
+        else score[i] = NEG_INF;
+    }
+
+    while (true) {
+        Top2 w = top2_reduce(loc, WAVE);
+        if (lane == 0) { s_w1[wid] = w.k1; s_w2[wid] = w.k2; }
+        __syncthreads();
+        if (wid == 0) {
+            // 16 per-wave pairs on lanes 0..15: four steps reach lane 0
+            Top2 b = {0ull, 0ull};
+            if (lane < SC_WAVES) { b.k1 = s_w1[lane]; b.k2 = s_w2[lane]; }
+            b = top2_reduce(b, SC_WAVES);
+            // lane 0 of wave 0 is thread 0, the only writer of the
+            // counters, the log, slot and (inside a run) score
+            if (lane == 0) {
+                int go = 0;
+                if (b.k1 != 0ull && s_remaining > 0)
+                    go = (slot[spread_key_node(b.k1)] >= 0 || s_cursor < K)
+                        ? 1 : 0;
+                s_best = b.k1;
+                s_runner = b.k2;
+                s_go = go;
+            }
+        }
+        __syncthreads();
+        if (!s_go) break;                    // block-uniform
+        const int b = spread_key_node(s_best);
+
+        if (tid == 0) {
+            const unsigned long long runner = s_runner;
+            int sl = slot[b];
+            int k = 0;
+            if (sl >= 0) {
+                k = log_counts[sl];
+            } else {
+                sl = s_cursor;
+                s_cursor = sl + 1;
+                slot[b] = sl;
+                log_nodes[sl] = b;
+            }
+            const int c = cap[b];
+            int rem = s_remaining;
+            float ns;
+            do {
+                k += 1;
+                rem -= 1;
+                ns = k >= c ? NEG_INF : node_score_one<false>(
+                    b, alloc, used, extra, nullptr, nullptr, nullptr, req,
+                    0, nullptr, nullptr, w_least, w_most, w_bal, dim_w,
+                    wsum, bias, N, R, 0, k).s;
+            } while (rem > 0 && ns > NEG_INF && spread_key(ns, b) > runner);
+            log_counts[sl] = k;
+            s_remaining = rem;
+            score[b] = ns;
+        }
+        __syncthreads();
+        // the winner's owner takes the new score into its top two
+        if (tid == (b & (SC_THREADS - 1))) {
+            loc.k1 = 0ull; loc.k2 = 0ull;
+            for (int i = tid; i < N; i += SC_THREADS) {
+                float s = score[i];
+                if (s > NEG_INF) loc = top2_offer(loc, spread_key(s, i));
+            }
+        }
+    }
+
+    __syncthreads();
+    const int total = s_budget - s_remaining;
+    const int cursor = s_cursor;
+    const bool revert = (fuse_min >= 0) && (total < fuse_min);
+
+    if (revert) {
+        // single-class gang failed: nothing was applied, the log keeps its
+        // nodes with zeroed counts
+        for (int e = tid; e < cursor; e += SC_THREADS) log_counts[e] = 0;
+        if (tid == 0) { *log_len = cursor; *placed = 0; }
+    } else {
+        dev_commit_log(log_nodes, log_counts, cursor, total, req, used,
+                       queue_alloc, log_len, placed, job_placed, N, R);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -2564,6 +2775,29 @@ void vamd_spread_multi_count_sub(
 }
 
 int vamd_spread_multi_lds_domains(void) { return SM_LDS_DOMAINS; }
+
+void vamd_rescore_select(
+    const float* alloc, float* used, const float* extra,
+    const uint8_t* ready, const int64_t* taints, const int64_t* planes,
+    const float* req, int64_t tolerated, const int64_t* require,
+    const int64_t* forbid, float w_least, float w_most, float w_bal,
+    const float* dim_w, const float* bias, float* score, const int* cap,
+    int ntasks, float* queue_alloc, const float* queue_limit,
+    int* log_nodes, int* log_counts, int* log_len, int* placed,
+    int* job_placed, int fuse_min, void* slot, int N, int R, int W, int K,
+    hipStream_t stream)
+{
+    // readiness, taints and label planes are already in `score`: a node
+    // that failed them holds -inf and is never scored again
+    (void)ready; (void)taints; (void)planes; (void)tolerated;
+    (void)require; (void)forbid; (void)W;
+    hipLaunchKernelGGL(vamd::rescore_select_kernel, dim3(1),
+                       dim3(SC_THREADS), 0, stream, alloc, used, extra, req,
+                       w_least, w_most, w_bal, dim_w, bias, score, cap,
+                       ntasks, queue_alloc, queue_limit, log_nodes,
+                       log_counts, log_len, placed, job_placed, fuse_min,
+                       (int*)slot, N, R, K);
+}
 
 int vamd_device_max_cards(void) { return vamd::CardPolicy::WIDTH; }
 

@@ -154,6 +154,31 @@ __attribute__((weak)) void vamd_spread_multi_count_sub(
 // Largest sum of D over the rules of one vamd_spread_multi_select.
 __attribute__((weak)) int vamd_spread_multi_lds_domains(void);
 
+// --- re-scoring select (nodeorder exact) -------------------------------------
+//
+// vamd_select_commit with the chosen node scored again after EVERY placement
+// (after vamd_score_cap and any cap or mask launcher; ONE workgroup).  It
+// takes the score inputs of vamd_fused_score_select: the score of a node with
+// k instances staged is the vamd_score_cap formula on
+// used_k = fma(k, req, used), bit for bit, or -inf when the node is full or
+// the formula's fit test fails there; no other node's score moves.  `score`
+// is consumed, `cap` only read; `slot` holds 4*N bytes.  The log carries one
+// (node, count) entry per node in order of first placement, so everything
+// that reads the log of vamd_select_commit reads this one.  Log entries past
+// *log_len are left as they were, as by the other selects.  Weak, like the
+// launchers above: the runner calls it only for a class flagged in
+// class_rescore.
+__attribute__((weak)) void vamd_rescore_select(
+    const float* alloc, float* used, const float* extra,
+    const uint8_t* ready, const int64_t* taints, const int64_t* planes,
+    const float* req, int64_t tolerated, const int64_t* require,
+    const int64_t* forbid, float w_least, float w_most, float w_bal,
+    const float* dim_w, const float* bias, float* score, const int* cap,
+    int ntasks, float* queue_alloc, const float* queue_limit,
+    int* log_nodes, int* log_counts, int* log_len, int* placed,
+    int* job_placed, int fuse_min, void* slot, int N, int R, int W, int K,
+    hipStream_t stream);
+
 // --- per-unit packing: GPU slices on cards, CPU requests on NUMA zones ------
 //
 // A pod takes its request from the units of a node; the rule is the host's
@@ -361,6 +386,10 @@ struct VamdCycle {
     // pairs; the class is multi-rule when n >= 2 and then also carries rule 0
     // in class_group / class_skew with mode 0
     const int32_t* class_spread_rules;  // HOST [C, 9]
+    // re-scoring block: live when both are set.  A class with a nonzero
+    // flag has its chosen node scored again after every placement
+    const int32_t* class_rescore;  // HOST [C]
+    int32_t* rescore_slot;         // [N] scratch of vamd_rescore_select
 };
 
 // Device copies of the descriptor arrays (chain and megacycle paths).
@@ -429,6 +458,15 @@ void vamd_megacycle(const VamdCycle& cy, const VamdDevDescs& dd,
 //     [vamd_device_commit] -> vamd_numa_commit, and its multi-class revert
 //     runs vamd_numa_revert as well.  With the block dead nothing changes a
 //     single launch.
+//   * A re-scoring class (re-scoring block live, class_rescore[c] != 0)
+//     always takes the split path: vamd_score_cap -> [vamd_device_cap] ->
+//     [vamd_numa_cap] -> [vamd_domain_mask, modes 1/2/3] ->
+//     vamd_rescore_select -> [count update] -> [commits] — never the fused,
+//     bulk, chain or megacycle path (a chain run breaks at it, a megacycle
+//     plan that holds one runs per class).  Its reverts are those of its
+//     domain rule.  A spread class (mode 0) keeps its own select with static
+//     scores whatever the flag says; the runner says so once on stderr.
+//     With the block dead nothing changes a single launch.
 // Returns 0; nonzero, before any HIP call, when cy->struct_size is not
 // sizeof(VamdCycle).
 int vamd_run_cycle(const VamdCycle* cy, hipStream_t stream);

@@ -77,7 +77,8 @@ class VamdCycle(Structure):
         (n, c_void_p) for n in (
             "zone_free", "class_numa_req", "numa_assign")] + [
         ("zone_Z", c_int32), ("_pad3", c_int32),
-        ("class_spread_rules", c_void_p)]
+        ("class_spread_rules", c_void_p),
+        ("class_rescore", c_void_p), ("rescore_slot", c_void_p)]
 
 
 def _load():
@@ -118,6 +119,7 @@ def _load():
             "the loaded kernel library and this module disagree on "
             "SPREAD_MULTI_LDS_DOMAINS; rebuild (python -m "
             "volcano_amd.ops.build)")
+    lib.vamd_rescore_select.restype = None
     lib.vamd_device_cap.restype = None
     lib.vamd_device_commit.restype = None
     lib.vamd_device_revert.restype = None
@@ -324,6 +326,39 @@ def spread_multi_count_sub(flag, log_nodes, log_counts, log_len, rules):
     rs = _spread_rules("spread_multi_count_sub", rules, N)
     lib.vamd_spread_multi_count_sub(
         _p(flag), _p(log_nodes), _p(log_counts), _p(log_len), rs, c_int(N),
+        c_int(K), _stream())
+
+
+def rescore_select(alloc_t, used_t, extra_t, ready, taints, planes_t, req,
+                   tolerated, require, forbid, w_least, w_most, w_bal, dim_w,
+                   bias, score, cap, ntasks, queue_alloc_row, queue_limit_row,
+                   log_nodes, log_counts, log_len, placed, job_placed,
+                   fuse_min, slot=None):
+    """``select_commit`` with the chosen node scored again after every
+    placement (after ``score_cap`` and any cap or mask op, whose inputs it
+    takes as well).  ``score`` is consumed; ``slot`` holds N int32."""
+    lib = _load()
+    R, N = alloc_t.shape
+    W = planes_t.shape[0]
+    K = log_nodes.shape[0]
+    if score.shape[0] != N or cap.shape[0] != N:
+        raise ValueError("rescore_select: score and cap need one entry per "
+                         "node")
+    if K < 1 or log_counts.shape[0] != K:
+        raise ValueError("rescore_select: log_nodes/log_counts differ in "
+                         "length or are empty")
+    if slot is None:
+        slot = torch.empty(max(N, 1), dtype=torch.int32, device=score.device)
+    elif slot.numel() * slot.element_size() < 4 * N:
+        raise ValueError("rescore_select: slot smaller than 4*N bytes")
+    lib.vamd_rescore_select(
+        _p(alloc_t), _p(used_t), _p(extra_t), _p(ready), _p(taints),
+        _p(planes_t), _p(req), c_int64(int(tolerated)), _p(require),
+        _p(forbid), c_float(w_least), c_float(w_most), c_float(w_bal),
+        _p(dim_w), _p(bias), _p(score), _p(cap), c_int(int(ntasks)),
+        _p(queue_alloc_row), _p(queue_limit_row), _p(log_nodes),
+        _p(log_counts), _p(log_len), _p(placed), _p(job_placed),
+        c_int(int(fuse_min)), _p(slot), c_int(N), c_int(R), c_int(W),
         c_int(K), _stream())
 
 
@@ -581,7 +616,7 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
               class_forbid, class_min, dim_w, queue_alloc, queue_limit,
               score_scratch, cap_scratch, log_nodes, log_counts, log_len,
               class_placed, job_placed, job_flag, sort_scratch=None,
-              spread=None, devices=None, numa=None):
+              spread=None, devices=None, numa=None, rescore=None):
     """One library call = one whole allocate cycle (plan built host-side).
 
     ``class_descs`` / ``job_descs`` are host buffers of ``VamdClassDesc`` /
@@ -612,7 +647,12 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
     ``numa`` (plans with NUMA-request classes only) is a dict:
     ``zone_free`` device i32 [Z, N], ``class_req`` host int32 numpy [C, 2]
     (cpu millicores, policy: 0 = none, 1 = hard, 2 = best-effort) and
-    ``assign`` device i32 [L, Z] (zeroed), parallel to the log."""
+    ``assign`` device i32 [L, Z] (zeroed), parallel to the log.
+
+    ``rescore`` (plans with re-scoring classes only) is a dict:
+    ``class_rescore`` host int32 numpy [C] (nonzero = the class's chosen
+    node is scored again after every placement) and ``slot`` device i32
+    [N] scratch."""
     lib = _load()
     R, N = alloc_t.shape
     cy = VamdCycle(
@@ -715,6 +755,18 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
         cy.class_numa_req = nreq.ctypes.data
         cy.numa_assign = _addr(numa["assign"])
         cy.zone_Z = Z
+    if rescore is not None:
+        flags = rescore["class_rescore"]
+        if flags.shape != (n_classes,) or flags.dtype != "int32" \
+                or not flags.flags["C_CONTIGUOUS"]:
+            raise ValueError("run_cycle: rescore.class_rescore must be "
+                             "int32 [C]")
+        slot = rescore["slot"]
+        if slot.dtype != torch.int32 or slot.numel() < N \
+                or not slot.is_contiguous():
+            raise ValueError("run_cycle: rescore.slot must be int32 [N]")
+        cy.class_rescore = flags.ctypes.data
+        cy.rescore_slot = _addr(slot)
     rc = lib.vamd_run_cycle(ctypes.byref(cy), _stream())
     if rc != 0:
         raise RuntimeError(

@@ -22,6 +22,8 @@ Kernel inventory (SURVEY.md §2.9 K1–K6 mapping):
   topology-spread bound checked before every placement, and its rollback.
 * ``affinity_select_commit`` — K2 select under an inter-pod (anti-)affinity
   domain rule checked before every placement (reverts: ``spread_revert``).
+* ``rescore_select_commit`` — K2 select that re-scores the chosen node after
+  every placement (reverts: ``cond_revert``).
 * ``hypernode_mask`` — network-topology domain choice from the live cap:
   a mask before ``select_commit`` (reverts: ``cond_revert``).
 * ``drf_share``      — K3 dominant share per job.
@@ -126,6 +128,8 @@ def select_commit(
     "sort by score desc, take cap each".  (The reference scores per task and
     samples 5 % of nodes — predicate_helper.go:45, scheduler_helper.go:56;
     we score ALL nodes, which strictly improves placement quality.)
+    ``rescore_select_commit`` is the exact variant that does re-score the
+    chosen node after every placement (nodeorder ``exact: true``).
     """
     N = score.shape[0]
     log_nodes.zero_()
@@ -526,6 +530,179 @@ def affinity_select_commit(
     queue_alloc += torch.tensor(float(total), device=dev) * req
     placed.fill_(total)
     job_placed.add_(total)
+
+
+def fma_f32(k: int, req: torch.Tensor, acc: torch.Tensor) -> torch.Tensor:
+    """``fma(float(k), req, acc)`` in f32 with ONE rounding, elementwise —
+    what ``acc_add`` of the kernels computes.  ``k * req`` is exact in f64;
+    the f64 sum is rounded to odd (TwoSum gives its error), after which the
+    rounding to f32 is the rounding of the exact value."""
+    import numpy as np
+    a = acc.detach().cpu().double().numpy()
+    p = float(k) * req.detach().cpu().double().numpy()
+    s = a + p
+    bb = s - a
+    err = (a - (s - bb)) + (p - bb)             # exact: a + p == s + err
+    toward = np.nextafter(s, np.where(err > 0, np.inf, -np.inf))
+    is_odd = (s.view(np.int64) & 1) == 1
+    s = np.where((err == 0) | is_odd | ~np.isfinite(s), s, toward)
+    return torch.from_numpy(s.astype(np.float32)).to(acc.device)
+
+
+def rescore_select_commit(
+    alloc: torch.Tensor,        # [N, R] f32 — the inputs of score_cap ...
+    used: torch.Tensor,         # [N, R] f32 — updated in place (staged)
+    extra: torch.Tensor,        # [N, R] f32
+    ready: torch.Tensor, taints: torch.Tensor, planes: torch.Tensor,
+    req: torch.Tensor, tolerated: int, require: torch.Tensor,
+    forbid: torch.Tensor, w_least: float, w_most: float, w_bal: float,
+    dim_w: torch.Tensor, bias: Optional[torch.Tensor],
+    score: torch.Tensor,        # [N] f32 from score_cap (and any mask)
+    cap: torch.Tensor,          # [N] i32 likewise
+    ntasks: int,
+    queue_alloc: torch.Tensor,  # [R] f32 in place
+    queue_limit: torch.Tensor,  # [R] f32
+    log_nodes: torch.Tensor,    # [K] i32 (K ≥ min(ntasks, N))
+    log_counts: torch.Tensor,   # [K] i32
+    log_len: torch.Tensor,      # [] i32
+    placed: torch.Tensor,       # [] i32
+    job_placed: torch.Tensor,   # [] i32
+    fuse_min: int = -1,         # ≥ 0: single-class gang minimum
+    score_fn=None,              # (node, k) -> float, replaces the formula
+) -> None:
+    """``select_commit`` with the chosen node re-scored after EVERY
+    placement (the per-task scoring of the reference's nodeorder).
+
+    A plain sequential loop on purpose — the source of truth the HIP
+    ``rescore_select_kernel`` must reproduce bit for bit.  It runs where
+    ``select_commit`` would, on ``score`` / ``cap`` as ``score_cap`` and any
+    cap or mask kernel left them.  ``rem[n] = cap[n]`` where
+    ``score[n] > -inf``, else 0.  Each step takes the node with the highest
+    score among those with ``rem > 0`` (ties to the lower index), places
+    ONE instance and re-scores that node alone: ``-inf`` once ``rem`` is 0,
+    else the ``score_cap`` formula (same operations, bias included) on
+    ``used_k = fma(float(k), req, used0)`` for its ``k`` staged instances —
+    the value the commit writes for a count of ``k``, one rounding — and
+    ``-inf`` when the formula's own fit test fails there.  The loop stops
+    at the budget ``min(ntasks, queue quota)``, when a new node would need
+    a log entry past ``K``, or when no node is left.
+
+    Log, ``used`` and counters follow ``spread_select_commit``: one
+    ``(node, count)`` entry per node in order of first placement, one
+    ``float(count) * req`` per entry.  A gang that misses ``fuse_min``
+    commits nothing and keeps its nodes with zeroed counts.
+    """
+    N = score.shape[0]
+    K = log_nodes.shape[0]
+    log_nodes.zero_()
+    log_counts.zero_()
+
+    headroom = queue_limit - queue_alloc
+    pos = req > EPS
+    per_dim = torch.where(pos, (headroom + EPS) / torch.clamp(req, min=EPS),
+                          torch.full_like(headroom, float(BIG_CAP)))
+    quota = int(per_dim.amin().clamp(min=0, max=float(BIG_CAP)).floor())
+    budget = min(int(ntasks), quota)
+
+    one_s = torch.empty(1, dtype=torch.float32, device=score.device)
+    one_c = torch.empty(1, dtype=torch.int32, device=score.device)
+
+    def formula(n: int, k: int) -> float:
+        # Readiness, taints and label planes do not move with usage and
+        # are already in ``score``: only the fit test is asked again.
+        row = slice(n, n + 1)
+        used_k = fma_f32(k, req, used[row])
+        score_cap(alloc[row], used_k, extra[row], torch.ones_like(ready[row]),
+                  torch.zeros_like(taints[row]), planes[row], req, 0,
+                  torch.zeros_like(require), torch.zeros_like(forbid),
+                  w_least, w_most, w_bal, dim_w,
+                  None if bias is None else bias[row], one_s, one_c)
+        return float(one_s)
+
+    rescore = formula if score_fn is None else score_fn
+    import heapq
+    rem = [int(c) if s > NEG_INF else 0
+           for s, c in zip(score.tolist(), cap.tolist())]
+    # every node that can still take an instance, once, under its live
+    # score: the smallest (-score, index) is the highest score, ties to the
+    # lower index (-0.0 and 0.0 compare equal)
+    heap = [(-s, n) for n, s in enumerate(score.tolist()) if rem[n] > 0]
+    heapq.heapify(heap)
+    slot = {}                   # node → log entry
+    nodes: list = []
+    counts: list = []
+    total = 0
+    while total < budget and heap:
+        best = heap[0][1]
+        e = slot.get(best)
+        if e is None:
+            if len(nodes) >= K:
+                break
+            e = slot[best] = len(nodes)
+            nodes.append(best)
+            counts.append(0)
+        heapq.heappop(heap)
+        counts[e] += 1
+        rem[best] -= 1
+        total += 1
+        s = rescore(best, counts[e]) if rem[best] > 0 else NEG_INF
+        if s > NEG_INF:
+            heapq.heappush(heap, (-s, best))
+
+    m = len(nodes)
+    dev = score.device
+    idx = torch.tensor(nodes, dtype=torch.long, device=dev)
+    c32 = torch.tensor(counts, dtype=torch.int32, device=dev)
+    log_nodes[:m] = idx.to(torch.int32)
+    log_len.fill_(m)
+    if fuse_min >= 0 and total < fuse_min:
+        placed.fill_(0)
+        return
+    log_counts[:m] = c32
+    used.index_add_(0, idx, c32.to(torch.float32).unsqueeze(1)
+                    * req.unsqueeze(0))
+    queue_alloc += torch.tensor(float(total), device=dev) * req
+    placed.fill_(total)
+    job_placed.add_(total)
+
+
+def domain_mask(score: torch.Tensor, cap: torch.Tensor,
+                dom_of: torch.Tensor, dom_count: torch.Tensor,
+                mode: int) -> None:
+    """The static mask the inter-pod rules collapse into (modes 1 and 2 of
+    the HIP ``domain_mask``): masked nodes get ``score = -inf``,
+    ``cap = 0``.  ``AFFINITY`` keeps the nodes of hosting domains, or, with
+    none, the domain of the best placeable node; ``ANTI_AFFINITY`` keeps
+    the best node of each empty domain with ``cap = 1``.  Followed by
+    ``select_commit`` and the count update it equals
+    ``affinity_select_commit``; a re-scoring class runs
+    ``rescore_select_commit`` behind it instead."""
+    if mode not in (AFFINITY, ANTI_AFFINITY):
+        raise ValueError("mode must be AFFINITY (1) or ANTI_AFFINITY (2)")
+    D = dom_count.shape[0]
+    sc, cp = score.tolist(), cap.tolist()
+    dom, cnt = dom_of.tolist(), dom_count.tolist()
+    ok = [0 <= d < D and c > 0 and s > NEG_INF
+          for s, c, d in zip(sc, cp, dom)]
+    heads = {}                  # domain → its best node
+    for n in range(len(sc)):
+        if ok[n] and (dom[n] not in heads or sc[n] > sc[heads[dom[n]]]):
+            heads[dom[n]] = n
+    if mode == AFFINITY:
+        hosting = any(c > 0 for c in cnt)
+        anchor = -1
+        if not hosting and heads:
+            anchor = dom[max(heads.values(), key=lambda n: (sc[n], -n))]
+        keep = [ok[n] and (cnt[dom[n]] > 0 or dom[n] == anchor)
+                for n in range(len(sc))]
+    else:
+        keep = [ok[n] and cnt[dom[n]] == 0 and heads[dom[n]] == n
+                for n in range(len(sc))]
+    out = ~torch.tensor(keep, dtype=torch.bool, device=score.device)
+    score[out] = NEG_INF
+    cap[out] = 0
+    if mode == ANTI_AFFINITY:
+        cap[~out] = 1
 
 
 HYPERNODE = 3                   # domain-rule mode of hypernode_mask

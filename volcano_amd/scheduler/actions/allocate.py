@@ -592,16 +592,24 @@ class _ExactRules:
     topology spread, inter-pod affinity, network topology (hypernode),
     device share and NUMA pinning.  A class that one of them claims is
     placed by a per-placement path of the cycle runner, loses the rule's
-    session-open constraint bit, and never joins a bundle.  None of them
-    applies under the soft-shard coordinator, whose conflict reconcile can
-    drop placements the kernel already counted."""
+    session-open constraint bit, and never joins a bundle.  The score itself
+    is the sixth (nodeorder): ``rescores`` says which classes have their
+    chosen node scored again after every placement.  None of them applies
+    under the soft-shard coordinator, whose conflict reconcile can drop
+    placements the kernel already counted."""
 
-    def __init__(self, ssn, plan: CyclePlan, enabled: bool):
+    def __init__(self, ssn, plan: CyclePlan, enabled: bool,
+                 weights=(1.0, 0.0, 0.0)):
         self.plan = plan
+        # (w_least, w_most, w_bal): with neither least nor balanced the
+        # chosen node's score never falls and the static fill already is the
+        # sequential result
+        self.score = enabled and bool(getattr(ssn, "score_exact", False)) \
+            and (weights[0] != 0 or weights[2] != 0)
         self.spread, self.affinity, self.hypernode, self.device, self.numa = [
             getattr(ssn, f"{name}_exact", None) if enabled else None
             for name in ("spread", "affinity", "hypernode", "device", "numa")]
-        self.any = any(x is not None for x in (
+        self.any = self.score or any(x is not None for x in (
             self.spread, self.affinity, self.hypernode, self.device,
             self.numa))
         self._group_of: Dict[tuple, int] = {}   # (rule, plugin group) → plan
@@ -630,6 +638,14 @@ class _ExactRules:
         if dom is None and dv is None and nu is None:
             return _NO_RULES
         return dom, dv, nu
+
+    def rescores(self, ntasks: int, claimed) -> bool:
+        """Whether a class of ``ntasks`` instances whose rules are
+        ``claimed`` re-scores per placement: only where that can change a
+        decision (two instances or more), and never a spread class, which
+        keeps its own select."""
+        return self.score and ntasks >= 2 and not (
+            claimed[0] is not None and claimed[0][0] == "spread")
 
     def resolve_subgroup(self, topo):
         """A SubGroupPolicy subgroup has its hypernode chosen on the device
@@ -721,7 +737,8 @@ class _PlanBuilder:
         self.weights = (w.get("least", 1.0), w.get("most", 0.0),
                         w.get("bal", 0.0))
         self.bias_fns = ssn.class_bias_fns
-        self.rules = _ExactRules(ssn, plan, action.coordinator is None)
+        self.rules = _ExactRules(ssn, plan, action.coordinator is None,
+                                 self.weights)
         self.open: ClassPlan = None     # the open bundle and its
         self.open_key = None            # (queue, signature)
         # (sig, qi) → (req, tolerated, require, forbid): one lookup per
@@ -886,11 +903,13 @@ class _PlanBuilder:
             if nominated and jb._nom:
                 elig_l[ix] = False
             elif rules.any:
-                first = next(iter(jb.task_status_index.get(
-                    PENDING_S, {}).values()), None)
-                if first is not None and \
-                        rules.resolve(jb, first) is not _NO_RULES:
-                    elig_l[ix] = False
+                pend = jb.task_status_index.get(PENDING_S, {})
+                first = next(iter(pend.values()), None)
+                if first is not None:
+                    claimed = rules.resolve(jb, first)
+                    if claimed is not _NO_RULES or \
+                            rules.rescores(len(pend), claimed):
+                        elig_l[ix] = False
 
     # -- constraint words and class construction --------------------------------------
     def class_words(self, tc, job, skip_topology: bool = False):
@@ -1002,7 +1021,8 @@ class _PlanBuilder:
         # bundle continuation: identical (queue, signature) run — append
         # the gang entry directly, skipping the TaskClass/ClassPlan/
         # constraint work bundle_in would discard anyway
-        if claimed is _NO_RULES and not self.bias_fns \
+        rescore = rules.any and rules.rescores(len(tasks), claimed)
+        if claimed is _NO_RULES and not rescore and not self.bias_fns \
                 and self.open is not None and self.open_key == (qi, sig):
             _append_entry(self.open, job, tasks, gang_min)
             return
@@ -1016,7 +1036,8 @@ class _PlanBuilder:
         cp = ClassPlan(tc, job.key, qi, *words, gang_min, *self.weights)
         if self.bias_fns:
             cp.bias = self.class_bias(tc, job)
-        if claimed is _NO_RULES and cp.bias is None:
+        cp.rescore = rescore
+        if claimed is _NO_RULES and cp.bias is None and not rescore:
             self.bundle_in(cp, job, qi, gang_min, sig)
         else:       # cp.never_bundles, known without asking
             if claimed is not _NO_RULES:
@@ -1053,6 +1074,7 @@ class _PlanBuilder:
             if claimed is not _NO_RULES:
                 rules.attach(cp, claimed, max(
                     job.min_available - job.occupied_count, min_needed))
+            cp.rescore = rules.any and rules.rescores(tc.count, claimed)
             classes.append(cp)
         if not classes:
             return

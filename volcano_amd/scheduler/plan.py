@@ -145,6 +145,12 @@ class ClassPlan:
     # the zones taken by numa_commit after the select.  Composes with every
     # domain rule and with ``device``; never combined with ``bundle``.
     numa: Optional[Tuple[int, int]] = None
+    # nodeorder ``exact: true``: the chosen node is scored again after every
+    # placement (rescore_select in place of select_commit, behind the same
+    # cap and mask kernels).  Composes with ``affinity``, ``hypernode``,
+    # ``device`` and ``numa``; a spread class keeps its own select with
+    # static scores; never combined with ``bundle``.
+    rescore: bool = False
 
     @property
     def ntasks(self) -> int:
@@ -153,9 +159,10 @@ class ClassPlan:
 
     @property
     def never_bundles(self) -> bool:
-        """Carries a bias row, a domain rule, a device or a NUMA request:
-        the class is placed on its own."""
-        return self.bias is not None or self.spread is not None \
+        """Carries a bias row, a domain rule, a device or a NUMA request, or
+        re-scores per placement: the class is placed on its own."""
+        return self.rescore or self.bias is not None \
+            or self.spread is not None \
             or self.affinity is not None or self.hypernode is not None \
             or self.device is not None or self.numa is not None
 
@@ -510,11 +517,18 @@ class CyclePlan:
                                         self.numa_state is None):
                 raise ValueError(f"class {c}: a numa class needs numa "
                                  "state and never bundles")
+            if cp.rescore and cp.bundle is not None:
+                raise ValueError(f"class {c}: re-scoring classes never "
+                                 "bundle")
             for rule in (cp.spread, cp.affinity):
                 if rule is not None and self.spread_groups[rule[0]].row >= 0:
                     raise ValueError(f"class {c}: group {rule[0]} is a "
                                      "hypernode group")
         self.log_total = off
+        # a spread class keeps its own select: its flag never reaches a runner
+        self.class_rescore = np.array(
+            [1 if cp.rescore and cp.spread is None else 0
+             for cp in self.classes], dtype=np.int32)
         lens = np.fromiter((jp.class_end - jp.class_begin
                             for jp in self.jobs), dtype=np.int64,
                            count=len(self.jobs))
@@ -623,6 +637,25 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
             if cp.numa is not None and cp.numa[1] == ref.NUMA_HARD:
                 ref.numa_cap(score, cap, zones, cp.numa[0])
             sl = slice(cp.log_off, cp.log_off + cp.log_cap)
+            def select():
+                # the static fill, or the per-placement re-score behind the
+                # same score, cap and mask
+                if not plan.class_rescore[c]:
+                    return ref.select_commit(
+                        score, cap, req, cp.ntasks, used,
+                        plan.queue_alloc[cp.queue_idx],
+                        plan.queue_limit[cp.queue_idx],
+                        log_nodes[sl], log_counts[sl], log_len[c],
+                        class_placed[c], job_placed[j])
+                return ref.rescore_select_commit(
+                    alloc, used, extra, nt.ready.bool(), nt.taint_mask,
+                    planes, req, cp.tolerated, require, forbid, cp.w_least,
+                    cp.w_most, cp.w_bal, dim_w, b, score, cap, cp.ntasks,
+                    plan.queue_alloc[cp.queue_idx],
+                    plan.queue_limit[cp.queue_idx],
+                    log_nodes[sl], log_counts[sl], log_len[c],
+                    class_placed[c], job_placed[j])
+
             if single:
                 # a discarded single-class gang leaves no trace (the HIP
                 # selects commit from the log only when the gang holds):
@@ -650,11 +683,16 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
                 g = cp.hypernode
                 ref.hypernode_mask(score, cap, sp_dom[g], sp_cnt[g],
                                    plan.spread_groups[g].leaves)
-                ref.select_commit(score, cap, req, cp.ntasks, used,
-                                  plan.queue_alloc[cp.queue_idx],
-                                  plan.queue_limit[cp.queue_idx],
-                                  log_nodes[sl], log_counts[sl], log_len[c],
-                                  class_placed[c], job_placed[j])
+                select()
+            elif cp.affinity is not None and plan.class_rescore[c]:
+                # the device's own composition: mask, select, count update
+                g, mode = cp.affinity
+                ref.domain_mask(score, cap, sp_dom[g], sp_cnt[g], mode)
+                select()
+                n = int(log_len[c])
+                sp_cnt[g].index_add_(
+                    0, sp_dom[g][log_nodes[sl][:n].long()].long(),
+                    log_counts[sl][:n])
             elif cp.affinity is not None:
                 g, mode = cp.affinity
                 ref.affinity_select_commit(
@@ -665,11 +703,7 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
                     class_placed[c], job_placed[j],
                     sp_dom[g], sp_cnt[g], mode)
             else:
-                ref.select_commit(score, cap, req, cp.ntasks, used,
-                                  plan.queue_alloc[cp.queue_idx],
-                                  plan.queue_limit[cp.queue_idx],
-                                  log_nodes[sl], log_counts[sl], log_len[c],
-                                  class_placed[c], job_placed[j])
+                select()
             if single:
                 need = max(jp.min_available - jp.occupied, cp.min_needed, 0)
                 flag = (class_placed[c] >= need).to(torch.uint8)
@@ -895,6 +929,14 @@ def run_plan_hip(plan: CyclePlan) -> CycleResult:
                                dtype=torch.int32, device=dev))
         plan.numa_plane = numa["zone_free"]
 
+    # re-scoring classes: the flag column stays host-side for the runner;
+    # the block exists only when the plan has such a class
+    rescore = None
+    if plan.class_rescore.any():
+        rescore = dict(
+            class_rescore=plan.class_rescore,
+            slot=torch.empty(max(N, 1), dtype=torch.int32, device=dev))
+
     hip.run_cycle(
         ctypes.c_void_p(cds.ctypes.data), C,
         ctypes.c_void_p(jds.ctypes.data), len(plan.jobs),
@@ -902,7 +944,8 @@ def run_plan_hip(plan: CyclePlan) -> CycleResult:
         nt.planes_t, bias, bias_rows, class_req, class_tol, class_require,
         class_forbid, class_min, dim_w, q_alloc, q_limit, score, cap,
         log_nodes, log_counts, log_len, class_placed, job_placed, job_flag,
-        sort_scratch, spread=spread, devices=devices, numa=numa)
+        sort_scratch, spread=spread, devices=devices, numa=numa,
+        rescore=rescore)
 
     res = CycleResult(plan, log_nodes.cpu().numpy(),
                       log_counts.cpu().numpy(), log_len.cpu().numpy(),
