@@ -12,8 +12,6 @@
 
 #include "vamd_api.h"
 
-#include <atomic>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
@@ -115,6 +113,8 @@ struct ClassView {
     VamdSpreadRules multi;
     // the chosen node is scored again after every placement
     bool rescore;
+    // a spread class (mode 0) that does so in its own select
+    bool spread_rescore;
 };
 
 struct Runner {
@@ -182,7 +182,7 @@ struct Runner {
             cy.log_len + c, cy.class_placed + c, cy.job_placed + j,
             cy.job_flag + j, single ? gang_fuse_min(job, cd) : -1,
             g, 0, 0, 0, nullptr, nullptr, dev_of(c), numa_of(c), {},
-            rescore_of(c)};
+            rescore_of(c), false};
         if (g >= 0) {
             v.mode = cy.class_mode != nullptr ? cy.class_mode[c] : 0;
             if (v.mode == 0) v.skew = cy.class_skew[c];
@@ -204,6 +204,9 @@ struct Runner {
             }
             v.multi.n = n;
         }
+        v.spread_rescore = g >= 0 && v.mode == 0 &&
+            cy.class_spread_rescore != nullptr &&
+            cy.class_spread_rescore[c] != 0;
         return v;
     }
 
@@ -260,6 +263,23 @@ struct Runner {
             v.queue_alloc, v.queue_limit, v.log_nodes, v.log_counts,
             v.log_len, v.placed, v.job_placed, v.multi, v.fuse_min,
             cy.domain_scratch, cy.N, cy.R, v.cd.log_cap, stream);
+    }
+
+    void spread_rescore_select(const ClassView& v) const {
+        // one rule travels as a rule set of one; slot: the first 4*N bytes
+        // of the domain scratch
+        VamdSpreadRules rules = v.multi;
+        if (rules.n < 2) {
+            rules.r[0] = {v.dom_of, v.dom_count, v.D, v.skew};
+            rules.n = 1;
+        }
+        vamd_spread_rescore_select(
+            cy.alloc, cy.used, v.pl.ext, v.req, v.cd.w_least, v.cd.w_most,
+            v.cd.w_bal, cy.dim_w, v.pl.bias, cy.score_scratch,
+            cy.cap_scratch, v.cd.ntasks, v.queue_alloc, v.queue_limit,
+            v.log_nodes, v.log_counts, v.log_len, v.placed, v.job_placed,
+            rules, v.fuse_min, cy.domain_scratch, cy.N, cy.R, v.cd.log_cap,
+            stream);
     }
 
     void domain_mask(const ClassView& v) const {
@@ -356,15 +376,10 @@ struct Runner {
             // topology spread: eligibility moves with every single
             // placement, so always the spread select, whatever the class
             // size; with several rules the node-scan select that intersects
-            // them
-            if (v.rescore) {
-                static std::atomic_flag said = ATOMIC_FLAG_INIT;
-                if (!said.test_and_set())
-                    fprintf(stderr, "vamd: a topology-spread class keeps "
-                            "static scores within the class; its re-score "
-                            "flag is ignored\n");
-            }
-            if (v.multi.n >= 2) spread_multi_select(v);
+            // them; with its re-score flag the select that also scores the
+            // chosen node again, for one rule or several
+            if (v.spread_rescore) spread_rescore_select(v);
+            else if (v.multi.n >= 2) spread_multi_select(v);
             else spread_select(v);
         } else {
             // inter-pod affinity / keyed anti-affinity / network topology:

@@ -1469,6 +1469,268 @@ spread_multi_select_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// K2 select under 1..4 topology-spread constraints that also RE-SCORES the
+// chosen node after every placement (topologyspread exact + nodeorder exact)
+// — oracle: reference.py spread_rescore_select_commit.  Replicas spread over
+// zones AND land on the least-requested node inside each zone.  Neither
+// neighbour stretches to it: the per-domain heads of spread_select_kernel go
+// stale with every falling score, and the runs of rescore_select_kernel stay
+// on one node, which a spread rule forbids.  So one instance per round:
+//
+//   * eligibility is spread_multi_select_kernel's: one bit per domain in the
+//     32 KB LDS bitmaps, m_r / atmin_r owned by thread 0, the ballot recount
+//     when a minimum rises, the same prologue (dead nodes leave the score
+//     vector, slot = -1) and the same limits.
+//   * every round every thread walks its 1024-stride slice of the nodes for
+//     the best ELIGIBLE key (spread_key), as spread_multi_select_kernel
+//     does.  A per-thread cache of that key, rescanned only by the winner's
+//     owner, by threads whose cached node lost a bit and by everyone after a
+//     recount, was built and measured against this: one workgroup on an idle
+//     CU is bound by latency, not by work, and the owner's walk sits on the
+//     critical path of every round anyway, so the cache was within the noise
+//     under a hostname rule and 4-7 % slower under a zone rule, where most
+//     rounds pay the check AND the walk (profiles/BENCH_NOTES.md).
+//   * the winner is scored again by thread 0 through node_score_one with its
+//     staged count k = log_counts[slot] and the static predicates off, as in
+//     rescore_select_kernel: the bits score_cap_kernel would write on a plane
+//     holding used_k = fma(k, req, used); -inf once k reaches cap (`cap` is
+//     only read) or the formula's fit test fails.
+//   * one round = ONE 64-bit block max reduce (wave shuffles, 16 partials
+//     through LDS), as in spread_multi_select_kernel.
+//
+// Barrier conventions of dev_select_commit: thread 0 owns every counter, the
+// log, slot, the counts, the closing bits and the winner's score, and
+// publishes go and the recount mask together; exits and the recount are
+// read block-uniformly after a barrier; no barrier under divergent control
+// flow.  The loop never writes `used` (log-first): a gang that misses
+// fuse_min gives its counts back with integer atomics and skips
+// dev_commit_log.
+// ---------------------------------------------------------------------------
+
+// best eligible key of the calling thread's slice (0: none).  The score and
+// the domain ids are loaded unconditionally, four nodes in flight.  `score`
+// is the kernel's live vector (thread 0 writes it between two barriers).
+DEVINL unsigned long long sr_scan(
+    const float* score, const VamdSpreadRules& rules,
+    int n_rules, const unsigned* s_open, const int* s_base, int N)
+{
+    unsigned long long loc = 0ull;
+#pragma unroll 4
+    for (int i = threadIdx.x; i < N; i += SP_THREADS) {
+        const float s = score[i];
+        int dom[SM_RULES];
+#pragma unroll
+        for (int r = 0; r < SM_RULES; ++r)
+            dom[r] = r < n_rules ? rules.r[r].dom_of[i] : 0;
+        // only a live node has its domains inside [0, D_r)
+        const bool live = s > NEG_INF;
+        bool open = live;
+#pragma unroll
+        for (int r = 0; r < SM_RULES; ++r)
+            if (r < n_rules)
+                open &= sm_open(s_open + s_base[r], live ? dom[r] : 0);
+        if (open) {
+            const unsigned long long k = spread_key(s, i);
+            if (k > loc) loc = k;
+        }
+    }
+    return loc;
+}
+
+// what thread 0 scores the winner with.  It parks these in LDS in the
+// prologue and reads them back per round: as kernel arguments they would sit
+// in SGPRs through the whole loop, next to the four rules, and spill.
+struct SrScoreArgs {
+    const float* alloc; const float* used; const float* extra;
+    const float* req; const float* dim_w; const float* bias;
+    float w_least, w_most, w_bal, wsum;
+};
+
+__global__ void __launch_bounds__(SP_THREADS)
+spread_rescore_select_kernel(
+    const float* __restrict__ alloc, float* __restrict__ used,
+    const float* __restrict__ extra, const float* __restrict__ req,
+    float w_least, float w_most, float w_bal,
+    const float* __restrict__ dim_w, const float* __restrict__ bias,
+    float* __restrict__ score,        // [N] consumed: holds the live scores
+    const int* __restrict__ cap,      // [N]
+    int ntasks,
+    float* __restrict__ queue_alloc, const float* __restrict__ queue_limit,
+    int* __restrict__ log_nodes, int* __restrict__ log_counts,
+    int* __restrict__ log_len, int* __restrict__ placed,
+    int* __restrict__ job_placed,
+    const VamdSpreadRules rules,      // by value: dom_of / count / D / skew
+    int fuse_min,
+    int* __restrict__ slot,           // [N] scratch: node -> log entry
+    int N, int R, int K)
+{
+    __shared__ unsigned s_open[SM_LDS_WORDS + 2 * SM_RULES];
+    __shared__ unsigned long long s_wkey[SP_WAVES];
+    __shared__ int s_part[SM_RULES][SP_WAVES];
+    __shared__ int s_base[SM_RULES];    // word offset of rule r's bitmap
+    __shared__ int s_m[SM_RULES];       // min(count_r) for the coming round
+    __shared__ int s_atmin[SM_RULES];   // #domains of rule r sitting at s_m[r]
+    __shared__ int s_budget;
+    __shared__ int s_cursor;
+    __shared__ int s_total;
+    __shared__ int s_go;
+    __shared__ int s_recount;           // mask of rules whose minimum rose
+    __shared__ SrScoreArgs s_args;      // thread 0 only
+
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wid = tid / WAVE;
+    const int n_rules = rules.n;
+    const int all_rules = (1 << n_rules) - 1;
+
+    if (tid == 0) {
+        long long b = dev_queue_budget(req, queue_limit, queue_alloc, ntasks,
+                                       R);
+        s_budget = (n_rules > 0 && b > 0)
+            ? (int)min(b, (long long)INT32_MAX) : 0;
+        s_cursor = 0;
+        s_total = 0;
+        // a wave step of the recount covers 64 domains = two words
+        int base = 0;
+        for (int r = 0; r < n_rules; ++r) {
+            s_base[r] = base;
+            base += 2 * ((rules.r[r].D + WAVE - 1) / WAVE);
+        }
+        float wsum = 0.f;
+        for (int r = 0; r < R; ++r) wsum += dim_w[r];
+        s_args = {alloc, used, extra, req, dim_w, bias, w_least, w_most,
+                  w_bal, fmaxf(wsum, EPS)};
+    }
+
+    // nodes that can never take an instance leave the score vector
+    for (int i = tid; i < N; i += SP_THREADS) {
+        slot[i] = -1;
+        bool ok = score[i] > NEG_INF && cap[i] > 0;
+        for (int r = 0; r < n_rules; ++r) {
+            const int d = rules.r[r].dom_of[i];
+            ok = ok && d >= 0 && d < rules.r[r].D;
+        }
+        if (!ok) score[i] = NEG_INF;
+    }
+
+    // initial minimum per rule: per-wave partial minima, folded by thread 0
+    for (int r = 0; r < n_rules; ++r) {
+        int lmin = INT32_MAX;
+        for (int d = tid; d < rules.r[r].D; d += SP_THREADS)
+            lmin = min(lmin, rules.r[r].count[d]);
+        for (int off = WAVE / 2; off > 0; off >>= 1)
+            lmin = min(lmin, __shfl_down(lmin, off));
+        if (lane == 0) s_part[r][wid] = lmin;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int r = 0; r < n_rules; ++r) {
+            int m = INT32_MAX;
+            for (int w = 0; w < SP_WAVES; ++w) m = min(m, s_part[r][w]);
+            s_m[r] = m;
+        }
+    }
+    __syncthreads();
+    sm_recount(rules, all_rules, s_open, s_base, s_m, s_part);
+    __syncthreads();
+    if (tid == 0) sm_fold(all_rules, s_atmin, s_part);
+
+    const int budget = s_budget;
+    for (int it = 0; it < budget; ++it) {
+        const unsigned long long wk = wave_max_u64(
+            sr_scan(score, rules, n_rules, s_open, s_base, N));
+        if (lane == 0) s_wkey[wid] = wk;
+        __syncthreads();
+        if (wid == 0) {
+            unsigned long long k = lane < SP_WAVES ? s_wkey[lane] : 0ull;
+            for (int off = SP_WAVES / 2; off > 0; off >>= 1) {
+                unsigned long long o = __shfl_down(k, off);
+                k = o > k ? o : k;
+            }
+            // lane 0 of wave 0 is thread 0, the only writer of the counters,
+            // the log, slot, the counts, the closing bits, s_m / s_atmin and
+            // the winner's score
+            if (lane == 0) {
+                int go = 0, recount = 0;
+                if (k != 0ull) {
+                    const int node = spread_key_node(k);
+                    int sl = slot[node];
+                    if (sl >= 0 || s_cursor < K) {
+                        go = 1;
+                        // one thread, a uniform r: the rule is read from
+                        // the kernel arguments by index, not unrolled
+                        for (int r = 0; r < n_rules; ++r) {
+                            const int d = rules.r[r].dom_of[node];
+                            const int c = rules.r[r].count[d];
+                            const int m = s_m[r];
+                            rules.r[r].count[d] = c + 1;
+                            // one more would break the skew: shut
+                            if (c + 2 - m > rules.r[r].skew)
+                                s_open[s_base[r] + (d >> 5)] &=
+                                    ~(1u << (d & 31));
+                            // the last domain at the minimum moved up
+                            if (c == m && --s_atmin[r] == 0) {
+                                s_m[r] = m + 1;
+                                recount |= 1 << r;
+                            }
+                        }
+                        int kst = 1;
+                        if (sl < 0) {
+                            sl = s_cursor;
+                            s_cursor = sl + 1;
+                            slot[node] = sl;
+                            log_nodes[sl] = node;
+                        } else {
+                            kst = log_counts[sl] + 1;
+                        }
+                        log_counts[sl] = kst;
+                        const SrScoreArgs a = s_args;
+                        score[node] = kst >= cap[node]
+                            ? NEG_INF : node_score_one<false>(
+                                node, a.alloc, a.used, a.extra, nullptr,
+                                nullptr, nullptr, a.req, 0, nullptr, nullptr,
+                                a.w_least, a.w_most, a.w_bal, a.dim_w,
+                                a.wsum, a.bias, N, R, 0, kst).s;
+                        s_total += 1;
+                    }
+                }
+                s_go = go;
+                s_recount = recount;
+            }
+        }
+        __syncthreads();
+        if (!s_go) break;               // block-uniform
+        const int rc = s_recount;       // block-uniform
+        if (rc != 0) {
+            sm_recount(rules, rc, s_open, s_base, s_m, s_part);
+            __syncthreads();
+            if (tid == 0) sm_fold(rc, s_atmin, s_part);
+        }
+    }
+
+    __syncthreads();
+    const int total = s_total;
+    const int cursor = s_cursor;
+    const bool revert = (fuse_min >= 0) && (total < fuse_min);
+
+    if (revert) {
+        // single-class gang failed: nothing was applied to `used` yet; give
+        // the placements back to the counts of every rule
+        for (int e = tid; e < cursor; e += SP_THREADS) {
+            const int node = log_nodes[e];
+            const int cnt = log_counts[e];
+            for (int r = 0; r < n_rules; ++r)
+                atomicSub(rules.r[r].count + rules.r[r].dom_of[node], cnt);
+            log_counts[e] = 0;
+        }
+        if (tid == 0) { *log_len = cursor; *placed = 0; }
+    } else {
+        dev_commit_log(log_nodes, log_counts, cursor, total, req, used,
+                       queue_alloc, log_len, placed, job_placed, N, R);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Inter-pod (anti-)affinity over a topology key, enforced before EVERY
 // placement — oracle: reference.py affinity_select_commit.  Unlike spread
 // this needs no per-instance loop: for both modes the per-placement rule
@@ -2797,6 +3059,30 @@ void vamd_rescore_select(
                        ntasks, queue_alloc, queue_limit, log_nodes,
                        log_counts, log_len, placed, job_placed, fuse_min,
                        (int*)slot, N, R, K);
+}
+
+void vamd_spread_rescore_select(
+    const float* alloc, float* used, const float* extra, const float* req,
+    float w_least, float w_most, float w_bal, const float* dim_w,
+    const float* bias, float* score, const int* cap, int ntasks,
+    float* queue_alloc, const float* queue_limit, int* log_nodes,
+    int* log_counts, int* log_len, int* placed, int* job_placed,
+    VamdSpreadRules rules, int fuse_min, void* slot, int N, int R, int K,
+    hipStream_t stream)
+{
+    // the limits of vamd_spread_multi_select: a set outside them is launched
+    // with no rule at all, which places nothing and reports zero
+    long long domains = 0;
+    for (int r = 0; r < rules.n && r < SM_RULES; ++r)
+        domains += rules.r[r].D > 0 ? rules.r[r].D : SM_LDS_DOMAINS + 1;
+    if (rules.n < 1 || rules.n > SM_RULES || domains > SM_LDS_DOMAINS)
+        rules.n = 0;
+    hipLaunchKernelGGL(vamd::spread_rescore_select_kernel, dim3(1),
+                       dim3(SP_THREADS), 0, stream, alloc, used, extra, req,
+                       w_least, w_most, w_bal, dim_w, bias, score, cap,
+                       ntasks, queue_alloc, queue_limit, log_nodes,
+                       log_counts, log_len, placed, job_placed, rules,
+                       fuse_min, (int*)slot, N, R, K);
 }
 
 int vamd_device_max_cards(void) { return vamd::CardPolicy::WIDTH; }

@@ -179,6 +179,27 @@ __attribute__((weak)) void vamd_rescore_select(
     int* job_placed, int fuse_min, void* slot, int N, int R, int W, int K,
     hipStream_t stream);
 
+// --- re-scoring select under topology spread ---------------------------------
+//
+// vamd_spread_multi_select (1..VAMD_SPREAD_MAX_RULES rules, the same limits,
+// the same count updates and gang give-back) with the chosen node scored
+// again after EVERY placement, as vamd_rescore_select scores it: the formula
+// of vamd_score_cap on used_k = fma(k, req, used) for its k staged instances,
+// -inf once k reaches cap[node] or the fit test fails.  After vamd_score_cap
+// and any cap launcher; ONE workgroup.  `score` is consumed, `cap` only read;
+// `slot` holds 4*N bytes.  With scores that never fall within the class the
+// result is that of vamd_spread_multi_select; with rules that never bind,
+// that of vamd_rescore_select.  Weak, like the launchers above: the runner
+// calls it only for a class flagged in class_spread_rescore.
+__attribute__((weak)) void vamd_spread_rescore_select(
+    const float* alloc, float* used, const float* extra, const float* req,
+    float w_least, float w_most, float w_bal, const float* dim_w,
+    const float* bias, float* score, const int* cap, int ntasks,
+    float* queue_alloc, const float* queue_limit, int* log_nodes,
+    int* log_counts, int* log_len, int* placed, int* job_placed,
+    VamdSpreadRules rules, int fuse_min, void* slot, int N, int R, int K,
+    hipStream_t stream);
+
 // --- per-unit packing: GPU slices on cards, CPU requests on NUMA zones ------
 //
 // A pod takes its request from the units of a node; the rule is the host's
@@ -390,6 +411,10 @@ struct VamdCycle {
     // flag has its chosen node scored again after every placement
     const int32_t* class_rescore;  // HOST [C]
     int32_t* rescore_slot;         // [N] scratch of vamd_rescore_select
+    // live when set (and the domain-rule block is): a spread class (mode 0)
+    // with a nonzero flag runs vamd_spread_rescore_select, for one rule or
+    // several
+    const int32_t* class_spread_rescore;  // HOST [C]
 };
 
 // Device copies of the descriptor arrays (chain and megacycle paths).
@@ -464,9 +489,15 @@ void vamd_megacycle(const VamdCycle& cy, const VamdDevDescs& dd,
 //     vamd_rescore_select -> [count update] -> [commits] — never the fused,
 //     bulk, chain or megacycle path (a chain run breaks at it, a megacycle
 //     plan that holds one runs per class).  Its reverts are those of its
-//     domain rule.  A spread class (mode 0) keeps its own select with static
-//     scores whatever the flag says; the runner says so once on stderr.
-//     With the block dead nothing changes a single launch.
+//     domain rule.  A spread class (mode 0) never reads this flag: it has
+//     its own, below.  With the block dead nothing changes a single launch.
+//   * A spread class flagged in class_spread_rescore runs
+//     vamd_spread_rescore_select in place of vamd_spread_select /
+//     vamd_spread_multi_select, for one rule or several (one rule travels as
+//     a rule set of one; the slot is the first 4*N bytes of the domain
+//     scratch).  The caps before, the commits after and the multi-class
+//     reverts are those of the select it replaces.  With the column null
+//     nothing changes a single launch.
 // Returns 0; nonzero, before any HIP call, when cy->struct_size is not
 // sizeof(VamdCycle).
 int vamd_run_cycle(const VamdCycle* cy, hipStream_t stream);

@@ -78,7 +78,8 @@ class VamdCycle(Structure):
             "zone_free", "class_numa_req", "numa_assign")] + [
         ("zone_Z", c_int32), ("_pad3", c_int32),
         ("class_spread_rules", c_void_p),
-        ("class_rescore", c_void_p), ("rescore_slot", c_void_p)]
+        ("class_rescore", c_void_p), ("rescore_slot", c_void_p),
+        ("class_spread_rescore", c_void_p)]
 
 
 def _load():
@@ -120,6 +121,7 @@ def _load():
             "SPREAD_MULTI_LDS_DOMAINS; rebuild (python -m "
             "volcano_amd.ops.build)")
     lib.vamd_rescore_select.restype = None
+    lib.vamd_spread_rescore_select.restype = None
     lib.vamd_device_cap.restype = None
     lib.vamd_device_commit.restype = None
     lib.vamd_device_revert.restype = None
@@ -360,6 +362,38 @@ def rescore_select(alloc_t, used_t, extra_t, ready, taints, planes_t, req,
         _p(log_counts), _p(log_len), _p(placed), _p(job_placed),
         c_int(int(fuse_min)), _p(slot), c_int(N), c_int(R), c_int(W),
         c_int(K), _stream())
+
+
+def spread_rescore_select(alloc_t, used_t, extra_t, req, w_least, w_most,
+                          w_bal, dim_w, bias, score, cap, ntasks,
+                          queue_alloc_row, queue_limit_row, log_nodes,
+                          log_counts, log_len, placed, job_placed, rules,
+                          fuse_min, slot=None):
+    """``spread_multi_select`` under 1 to 4 rules with the chosen node scored
+    again after every placement, as ``rescore_select`` scores it (after
+    ``score_cap`` and any cap op).  ``score`` is consumed, ``cap`` only read;
+    ``slot`` holds N int32."""
+    lib = _load()
+    R, N = alloc_t.shape
+    K = log_nodes.shape[0]
+    if score.shape[0] != N or cap.shape[0] != N:
+        raise ValueError("spread_rescore_select: score and cap need one "
+                         "entry per node")
+    if K < 1 or log_counts.shape[0] != K:
+        raise ValueError("spread_rescore_select: log_nodes/log_counts differ "
+                         "in length or are empty")
+    rs = _spread_rules("spread_rescore_select", rules, N)
+    if slot is None:
+        slot = torch.empty(max(N, 1), dtype=torch.int32, device=score.device)
+    elif slot.numel() * slot.element_size() < 4 * N:
+        raise ValueError("spread_rescore_select: slot smaller than 4*N bytes")
+    lib.vamd_spread_rescore_select(
+        _p(alloc_t), _p(used_t), _p(extra_t), _p(req), c_float(w_least),
+        c_float(w_most), c_float(w_bal), _p(dim_w), _p(bias), _p(score),
+        _p(cap), c_int(int(ntasks)), _p(queue_alloc_row),
+        _p(queue_limit_row), _p(log_nodes), _p(log_counts), _p(log_len),
+        _p(placed), _p(job_placed), rs, c_int(int(fuse_min)), _p(slot),
+        c_int(N), c_int(R), c_int(K), _stream())
 
 
 def domain_mask(score, cap, dom_of, dom_count, mode, scratch=None):
@@ -636,7 +670,10 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
     ``count`` slice of a mode-3 group is its table.  An optional
     ``class_rules`` (host int32 numpy [C, 9]: n, then four (group, maxSkew)
     pairs) names every rule of the spread classes that have several (n >= 2;
-    rule 0 is also the class's ``class_group``/``class_skew``).
+    rule 0 is also the class's ``class_group``/``class_skew``).  An optional
+    ``class_rescore`` (host int32 numpy [C]) flags the spread classes whose
+    chosen node is scored again after every placement
+    (``spread_rescore_select``, for one rule or several).
 
     ``devices`` (plans with device-request classes only) is a dict: the
     card planes ``mem_used``/``cores_used``/``state`` device i32 [K, N],
@@ -720,6 +757,13 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
                                      f"{SPREAD_MULTI_LDS_DOMAINS} domains in "
                                      "all")
             cy.class_spread_rules = cr.ctypes.data
+        flags = spread.get("class_rescore")
+        if flags is not None:
+            if flags.shape != (n_classes,) or flags.dtype != "int32" \
+                    or not flags.flags["C_CONTIGUOUS"]:
+                raise ValueError("run_cycle: spread.class_rescore must be "
+                                 "int32 [C]")
+            cy.class_spread_rescore = flags.ctypes.data
     if devices is not None:
         K, _ = _unit_planes("run_cycle", _CARDS, (
             devices["mem_used"], devices["cores_used"], devices["state"]),

@@ -666,6 +666,128 @@ def rescore_select_commit(
     job_placed.add_(total)
 
 
+def spread_rescore_select_commit(
+    alloc: torch.Tensor, used: torch.Tensor, extra: torch.Tensor,
+    ready: torch.Tensor, taints: torch.Tensor, planes: torch.Tensor,
+    req: torch.Tensor, tolerated: int, require: torch.Tensor,
+    forbid: torch.Tensor, w_least: float, w_most: float, w_bal: float,
+    dim_w: torch.Tensor, bias: Optional[torch.Tensor],
+    score: torch.Tensor, cap: torch.Tensor, ntasks: int,
+    queue_alloc: torch.Tensor, queue_limit: torch.Tensor,
+    log_nodes: torch.Tensor, log_counts: torch.Tensor, log_len: torch.Tensor,
+    placed: torch.Tensor, job_placed: torch.Tensor,
+    rules,                      # as in spread_multi_select_commit
+    fuse_min: int = -1, score_fn=None,
+) -> None:
+    """``rescore_select_commit`` under the 1 to 4 spread rules of
+    ``spread_multi_select_commit`` (topologyspread and nodeorder both exact):
+    replicas spread over the domains AND take the best node by its live
+    score inside them.
+
+    A plain sequential loop — the source of truth of the HIP
+    ``spread_rescore_select_kernel``.  Per instance: among the nodes with
+    ``score > -inf`` whose domain is open under EVERY rule
+    (``cnt_r[d] + 1 - min(cnt_r) <= skew_r``, the minimum over all ``D_r``
+    domains) the best score wins, ties to the lower index; it takes ONE
+    instance; its domain's count rises under every rule; and it alone is
+    scored again as ``rescore_select_commit`` does it (``score_fn`` hook
+    included): the formula on ``fma_f32(k, req, used)`` for its ``k`` staged
+    instances, ``-inf`` once its capacity is used up or the fit test fails.
+    The loop stops at the budget, at a new node past the log's ``K`` entries,
+    or at the first state without an eligible node.
+
+    One ``(node, count)`` log entry per node in order of first placement, one
+    ``count * req`` per entry into ``used`` after the loop.  A gang that
+    misses ``fuse_min`` gives every count back and writes nothing else: the
+    log keeps its nodes with zeroed counts."""
+    rules = list(rules)
+    if not 1 <= len(rules) <= SPREAD_MAX_RULES:
+        raise ValueError(f"1 to {SPREAD_MAX_RULES} spread rules per class")
+    if any(int(skew) < 1 for _, _, skew in rules):
+        raise ValueError("max_skew must be >= 1")
+    N = score.shape[0]
+    K = log_nodes.shape[0]
+    log_nodes.zero_()
+    log_counts.zero_()
+
+    headroom = queue_limit - queue_alloc
+    pos = req > EPS
+    per_dim = torch.where(pos, (headroom + EPS) / torch.clamp(req, min=EPS),
+                          torch.full_like(headroom, float(BIG_CAP)))
+    quota = int(per_dim.amin().clamp(min=0, max=float(BIG_CAP)).floor())
+    budget = min(int(ntasks), quota)
+
+    one_s = torch.empty(1, dtype=torch.float32, device=score.device)
+    one_c = torch.empty(1, dtype=torch.int32, device=score.device)
+
+    def formula(n: int, k: int) -> float:
+        row = slice(n, n + 1)
+        score_cap(alloc[row], fma_f32(k, req, used[row]), extra[row],
+                  torch.ones_like(ready[row]), torch.zeros_like(taints[row]),
+                  planes[row], req, 0, torch.zeros_like(require),
+                  torch.zeros_like(forbid), w_least, w_most, w_bal, dim_w,
+                  None if bias is None else bias[row], one_s, one_c)
+        return float(one_s)
+
+    rescore = formula if score_fn is None else score_fn
+    sc = score.tolist()
+    doms = [d.tolist() for d, _, _ in rules]
+    cnts = [c.tolist() for _, c, _ in rules]
+    before = [list(c) for c in cnts]
+    skews = [int(s) for _, _, s in rules]
+    rem = [int(c) if s > NEG_INF and all(d[n] >= 0 for d in doms) else 0
+           for n, (s, c) in enumerate(zip(sc, cap.tolist()))]
+    slot = {}                   # node → log entry
+    nodes: list = []
+    counts: list = []
+    total = 0
+    while total < budget:
+        lows = [min(c) for c in cnts]
+        best = -1
+        for n in range(N):
+            if rem[n] > 0 and (best < 0 or sc[n] > sc[best]) and all(
+                    c[d[n]] + 1 - m <= k
+                    for c, d, m, k in zip(cnts, doms, lows, skews)):
+                best = n
+        if best < 0:
+            break
+        e = slot.get(best)
+        if e is None:
+            if len(nodes) >= K:
+                break
+            e = slot[best] = len(nodes)
+            nodes.append(best)
+            counts.append(0)
+        counts[e] += 1
+        rem[best] -= 1
+        total += 1
+        for c, d in zip(cnts, doms):
+            c[d[best]] += 1
+        s = rescore(best, counts[e]) if rem[best] > 0 else NEG_INF
+        sc[best] = s
+        if not s > NEG_INF:
+            rem[best] = 0
+
+    m = len(nodes)
+    dev = score.device
+    idx = torch.tensor(nodes, dtype=torch.long, device=dev)
+    c32 = torch.tensor(counts, dtype=torch.int32, device=dev)
+    log_nodes[:m] = idx.to(torch.int32)
+    log_len.fill_(m)
+    discard = fuse_min >= 0 and total < fuse_min
+    for (_, dom_count, _), c in zip(rules, before if discard else cnts):
+        dom_count.copy_(torch.tensor(c, dtype=torch.int32, device=dev))
+    if discard:
+        placed.fill_(0)
+        return
+    log_counts[:m] = c32
+    used.index_add_(0, idx, c32.to(torch.float32).unsqueeze(1)
+                    * req.unsqueeze(0))
+    queue_alloc += torch.tensor(float(total), device=dev) * req
+    placed.fill_(total)
+    job_placed.add_(total)
+
+
 def domain_mask(score: torch.Tensor, cap: torch.Tensor,
                 dom_of: torch.Tensor, dom_count: torch.Tensor,
                 mode: int) -> None:

@@ -639,13 +639,12 @@ class _ExactRules:
             return _NO_RULES
         return dom, dv, nu
 
-    def rescores(self, ntasks: int, claimed) -> bool:
-        """Whether a class of ``ntasks`` instances whose rules are
-        ``claimed`` re-scores per placement: only where that can change a
-        decision (two instances or more), and never a spread class, which
-        keeps its own select."""
-        return self.score and ntasks >= 2 and not (
-            claimed[0] is not None and claimed[0][0] == "spread")
+    def rescores(self, ntasks: int) -> bool:
+        """Whether a class of ``ntasks`` instances re-scores per placement:
+        only where that can change a decision (two instances or more), and
+        whatever rules claim it — a spread class re-scores inside its own
+        select."""
+        return self.score and ntasks >= 2
 
     def resolve_subgroup(self, topo):
         """A SubGroupPolicy subgroup has its hypernode chosen on the device
@@ -908,7 +907,7 @@ class _PlanBuilder:
                 if first is not None:
                     claimed = rules.resolve(jb, first)
                     if claimed is not _NO_RULES or \
-                            rules.rescores(len(pend), claimed):
+                            rules.rescores(len(pend)):
                         elig_l[ix] = False
 
     # -- constraint words and class construction --------------------------------------
@@ -1021,7 +1020,7 @@ class _PlanBuilder:
         # bundle continuation: identical (queue, signature) run — append
         # the gang entry directly, skipping the TaskClass/ClassPlan/
         # constraint work bundle_in would discard anyway
-        rescore = rules.any and rules.rescores(len(tasks), claimed)
+        rescore = rules.any and rules.rescores(len(tasks))
         if claimed is _NO_RULES and not rescore and not self.bias_fns \
                 and self.open is not None and self.open_key == (qi, sig):
             _append_entry(self.open, job, tasks, gang_min)
@@ -1074,7 +1073,7 @@ class _PlanBuilder:
             if claimed is not _NO_RULES:
                 rules.attach(cp, claimed, max(
                     job.min_available - job.occupied_count, min_needed))
-            cp.rescore = rules.any and rules.rescores(tc.count, claimed)
+            cp.rescore = rules.any and rules.rescores(tc.count)
             classes.append(cp)
         if not classes:
             return

@@ -148,8 +148,8 @@ class ClassPlan:
     # nodeorder ``exact: true``: the chosen node is scored again after every
     # placement (rescore_select in place of select_commit, behind the same
     # cap and mask kernels).  Composes with ``affinity``, ``hypernode``,
-    # ``device`` and ``numa``; a spread class keeps its own select with
-    # static scores; never combined with ``bundle``.
+    # ``device`` and ``numa``; a spread class takes spread_rescore_select,
+    # which holds its rules and re-scores; never combined with ``bundle``.
     rescore: bool = False
 
     @property
@@ -525,9 +525,13 @@ class CyclePlan:
                     raise ValueError(f"class {c}: group {rule[0]} is a "
                                      "hypernode group")
         self.log_total = off
-        # a spread class keeps its own select: its flag never reaches a runner
+        # a spread class re-scores inside a select of its own and has its own
+        # column: class_rescore stays 0 for it
         self.class_rescore = np.array(
             [1 if cp.rescore and cp.spread is None else 0
+             for cp in self.classes], dtype=np.int32)
+        self.class_spread_rescore = np.array(
+            [1 if cp.rescore and cp.spread is not None else 0
              for cp in self.classes], dtype=np.int32)
         lens = np.fromiter((jp.class_end - jp.class_begin
                             for jp in self.jobs), dtype=np.int64,
@@ -662,7 +666,18 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
                 # u + c*r - c*r is not u in f32 once usage comes in bytes
                 used_before = used.clone()
                 qa_before = plan.queue_alloc[cp.queue_idx].clone()
-            if cp.spread_rules is not None and len(cp.spread_rules) >= 2:
+            if plan.class_spread_rescore[c]:
+                ref.spread_rescore_select_commit(
+                    alloc, used, extra, nt.ready.bool(), nt.taint_mask,
+                    planes, req, cp.tolerated, require, forbid, cp.w_least,
+                    cp.w_most, cp.w_bal, dim_w, b, score, cap, cp.ntasks,
+                    plan.queue_alloc[cp.queue_idx],
+                    plan.queue_limit[cp.queue_idx],
+                    log_nodes[sl], log_counts[sl], log_len[c],
+                    class_placed[c], job_placed[j],
+                    [(sp_dom[g], sp_cnt[g], k)
+                     for g, k in cp.spread_rules or [cp.spread]])
+            elif cp.spread_rules is not None and len(cp.spread_rules) >= 2:
                 ref.spread_multi_select_commit(
                     score, cap, req, cp.ntasks, used,
                     plan.queue_alloc[cp.queue_idx],
@@ -890,6 +905,10 @@ def run_plan_hip(plan: CyclePlan) -> CycleResult:
                     cr[c, 1:1 + 2 * len(cp.spread_rules)] = \
                         np.asarray(cp.spread_rules, dtype=np.int32).ravel()
             spread["class_rules"] = cr
+        # spread classes that re-score per placement: the flag column stays
+        # host-side for the runner and exists only when the plan has one
+        if plan.class_spread_rescore.any():
+            spread["class_rescore"] = plan.class_spread_rescore
         plan.spread_counts = [count[int(o):int(o) + int(d)]
                               for o, d in zip(offs, lens)]
 
