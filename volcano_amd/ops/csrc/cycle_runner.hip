@@ -115,6 +115,9 @@ struct ClassView {
     bool rescore;
     // a spread class (mode 0) that does so in its own select
     bool spread_rescore;
+    // one weight per rule of a spread class; any nonzero = a soft rule
+    VamdSpreadWeights soft;
+    bool spread_soft;
 };
 
 struct Runner {
@@ -182,7 +185,7 @@ struct Runner {
             cy.log_len + c, cy.class_placed + c, cy.job_placed + j,
             cy.job_flag + j, single ? gang_fuse_min(job, cd) : -1,
             g, 0, 0, 0, nullptr, nullptr, dev_of(c), numa_of(c), {},
-            rescore_of(c), false};
+            rescore_of(c), false, {}, false};
         if (g >= 0) {
             v.mode = cy.class_mode != nullptr ? cy.class_mode[c] : 0;
             if (v.mode == 0) v.skew = cy.class_skew[c];
@@ -207,6 +210,15 @@ struct Runner {
         v.spread_rescore = g >= 0 && v.mode == 0 &&
             cy.class_spread_rescore != nullptr &&
             cy.class_spread_rescore[c] != 0;
+        if (g >= 0 && v.mode == 0 && cy.class_spread_soft != nullptr) {
+            const float* tw = cy.class_spread_soft +
+                (size_t)c * VAMD_SPREAD_MAX_RULES;
+            const int n = v.multi.n >= 2 ? v.multi.n : 1;
+            for (int k = 0; k < n; ++k) {
+                v.soft.tw[k] = tw[k];
+                v.spread_soft = v.spread_soft || tw[k] != 0.f;
+            }
+        }
         return v;
     }
 
@@ -280,6 +292,22 @@ struct Runner {
             v.log_nodes, v.log_counts, v.log_len, v.placed, v.job_placed,
             rules, v.fuse_min, cy.domain_scratch, cy.N, cy.R, v.cd.log_cap,
             stream);
+    }
+
+    void spread_soft_select(const ClassView& v) const {
+        // as spread_rescore_select, the weights beside the rules
+        VamdSpreadRules rules = v.multi;
+        if (rules.n < 2) {
+            rules.r[0] = {v.dom_of, v.dom_count, v.D, v.skew};
+            rules.n = 1;
+        }
+        vamd_spread_soft_select(
+            cy.alloc, cy.used, v.pl.ext, v.req, v.cd.w_least, v.cd.w_most,
+            v.cd.w_bal, cy.dim_w, v.pl.bias, cy.score_scratch,
+            cy.cap_scratch, v.cd.ntasks, v.queue_alloc, v.queue_limit,
+            v.log_nodes, v.log_counts, v.log_len, v.placed, v.job_placed,
+            rules, v.soft, v.spread_rescore ? 1 : 0, v.fuse_min,
+            cy.domain_scratch, cy.N, cy.R, v.cd.log_cap, stream);
     }
 
     void domain_mask(const ClassView& v) const {
@@ -377,8 +405,10 @@ struct Runner {
             // placement, so always the spread select, whatever the class
             // size; with several rules the node-scan select that intersects
             // them; with its re-score flag the select that also scores the
-            // chosen node again, for one rule or several
-            if (v.spread_rescore) spread_rescore_select(v);
+            // chosen node again, for one rule or several; with a soft rule
+            // the select that scores the rule's counts into every key
+            if (v.spread_soft) spread_soft_select(v);
+            else if (v.spread_rescore) spread_rescore_select(v);
             else if (v.multi.n >= 2) spread_multi_select(v);
             else spread_select(v);
         } else {

@@ -1731,6 +1731,321 @@ spread_rescore_select_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// K2 select under 1..4 topology-spread constraints of which some are SOFT
+// (whenUnsatisfiable: ScheduleAnyway) — oracle: reference.py
+// spread_soft_select_commit.  A soft rule r (tw_r != 0) never filters on
+// counts; it costs tw_r per member already in the node's domain:
+//
+//     pen(n)   = fma(tw_R, float(cnt_R[dom_R(n)]), ... fma(tw_1, ..., 0.0f))
+//     total(n) = score[n] - pen(n)
+//
+// over the soft rules in rule order, and the best total among the nodes open
+// under every HARD rule wins.  None of the neighbours stretches to it: a
+// static bias row cannot follow a term that moves for a whole domain with
+// every placement; the per-domain heads of spread_select_kernel are keyed on
+// the raw score, and two scores of one domain can round onto one total, where
+// the lower index wins and need not be the head; the runs of
+// rescore_select_kernel assume that only the winner's key moves.  So:
+//
+//   * hard rules are spread_multi_select_kernel's: one bit per domain in the
+//     32 KB LDS bitmaps, m_r / atmin_r owned by thread 0, the ballot recount
+//     when a minimum rises (sm_recount / sm_fold, masked to the hard rules).
+//     Their counts stay in global memory.
+//   * the counts of the soft rules sit back to back in s_cnt, a second LDS
+//     table of SS_LDS_DOMAINS int32 (28 KB): loaded once in the prologue,
+//     one word per soft rule incremented by thread 0 per placement, written
+//     back by the epilogue.  A gang that misses fuse_min simply skips the
+//     write-back: global memory still holds the counts it started from.
+//   * one round: every thread walks its 1024-stride slice; a live node open
+//     under every hard rule gathers one count per soft rule from s_cnt,
+//     folds them with fmaf in rule order and offers
+//     spread_key(score - pen, i); ONE 64-bit block max reduce (wave
+//     shuffles, 16 partials through LDS).  The penalty moves a whole domain
+//     at once, so every thread rescans every round: there is no per-thread
+//     cache and there are no runs.
+//   * thread 0 places one instance: log and slot, the staged count against
+//     cap (`cap` is only read), per-rule count, closing bit and atmin for a
+//     hard rule, the LDS word for a soft one.  With `rescore` it scores the
+//     winner again through node_score_one with the staged count, as
+//     spread_rescore_select_kernel does; without, the score stays until the
+//     capacity is used up.
+//
+// fmaf and the single subtraction are spelled out, so no contraction can
+// change the penalty (the library is built without packed f32).  Barrier
+// conventions of dev_select_commit: thread 0 owns every counter and table
+// word and publishes go and the recount mask together; exits and the recount
+// are read block-uniformly after a barrier; no barrier under divergent
+// control flow.
+// ---------------------------------------------------------------------------
+#define SS_LDS_DOMAINS 7168                 // 28 KB of soft counts
+
+// thread 0's placement state and what every thread reads per round, parked
+// in LDS so that the rules alone occupy the kernel's SGPRs
+struct SsArgs {
+    SrScoreArgs sc;
+    float* queue_alloc; int* log_len; int* placed; int* job_placed;
+    int rescore, fuse_min, K;
+};
+
+__global__ void __launch_bounds__(SP_THREADS)
+spread_soft_select_kernel(
+    const float* __restrict__ alloc, float* __restrict__ used,
+    const float* __restrict__ extra, const float* __restrict__ req,
+    float w_least, float w_most, float w_bal,
+    const float* __restrict__ dim_w, const float* __restrict__ bias,
+    float* __restrict__ score,        // [N] consumed: holds the live scores
+    const int* __restrict__ cap,      // [N]
+    int ntasks,
+    float* __restrict__ queue_alloc, const float* __restrict__ queue_limit,
+    int* __restrict__ log_nodes, int* __restrict__ log_counts,
+    int* __restrict__ log_len, int* __restrict__ placed,
+    int* __restrict__ job_placed,
+    const VamdSpreadRules rules,      // by value: dom_of / count / D / skew
+    const VamdSpreadWeights weights,  // by value: tw_r, 0 = hard rule
+    int rescore, int fuse_min,
+    int* __restrict__ slot,           // [N] scratch: node -> log entry
+    int N, int R, int K)
+{
+    __shared__ unsigned s_open[SM_LDS_WORDS + 2 * SM_RULES];
+    __shared__ int s_cnt[SS_LDS_DOMAINS];   // soft counts, rules back to back
+    __shared__ unsigned long long s_wkey[SP_WAVES];
+    __shared__ int s_part[SM_RULES][SP_WAVES];
+    __shared__ int s_base[SM_RULES];    // hard: word offset of the bitmap
+    __shared__ int s_sbase[SM_RULES];   // soft: offset into s_cnt
+    __shared__ float s_tw[SM_RULES];
+    __shared__ int s_m[SM_RULES];       // min(count_r) for the coming round
+    __shared__ int s_atmin[SM_RULES];   // #domains of rule r sitting at s_m[r]
+    __shared__ int s_hard;              // mask of the hard rules
+    __shared__ int s_budget;
+    __shared__ int s_cursor;
+    __shared__ int s_total;
+    __shared__ int s_go;
+    __shared__ int s_recount;           // mask of rules whose minimum rose
+    __shared__ SsArgs s_args;           // thread 0; the block's epilogue
+
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wid = tid / WAVE;
+    const int n_rules = rules.n;
+
+    if (tid == 0) {
+        long long b = dev_queue_budget(req, queue_limit, queue_alloc, ntasks,
+                                       R);
+        s_budget = (n_rules > 0 && b > 0)
+            ? (int)min(b, (long long)INT32_MAX) : 0;
+        s_cursor = 0;
+        s_total = 0;
+        // a wave step of the recount covers 64 domains = two words
+        int base = 0, sbase = 0, hard = 0;
+        for (int r = 0; r < SM_RULES; ++r) {
+            const float tw = r < n_rules ? weights.tw[r] : 0.f;
+            s_tw[r] = tw;
+            s_base[r] = 0;
+            s_sbase[r] = 0;
+            if (r >= n_rules) continue;
+            if (tw == 0.f) {
+                hard |= 1 << r;
+                s_base[r] = base;
+                base += 2 * ((rules.r[r].D + WAVE - 1) / WAVE);
+            } else {
+                s_sbase[r] = sbase;
+                sbase += rules.r[r].D;
+            }
+        }
+        s_hard = hard;
+        float wsum = 0.f;
+        for (int r = 0; r < R; ++r) wsum += dim_w[r];
+        s_args = {{alloc, used, extra, req, dim_w, bias, w_least, w_most,
+                   w_bal, fmaxf(wsum, EPS)}, queue_alloc, log_len, placed,
+                  job_placed, rescore, fuse_min, K};
+    }
+
+    // nodes that can never take an instance leave the score vector
+    for (int i = tid; i < N; i += SP_THREADS) {
+        slot[i] = -1;
+        bool ok = score[i] > NEG_INF && cap[i] > 0;
+        for (int r = 0; r < n_rules; ++r) {
+            const int d = rules.r[r].dom_of[i];
+            ok = ok && d >= 0 && d < rules.r[r].D;
+        }
+        if (!ok) score[i] = NEG_INF;
+    }
+    __syncthreads();
+    const int hard = s_hard;            // block-uniform
+
+    // hard rules: per-wave partial minima, folded by thread 0; soft rules:
+    // the counts move into LDS
+    for (int r = 0; r < n_rules; ++r) {
+        const int* __restrict__ count = rules.r[r].count;
+        const int D = rules.r[r].D;
+        if ((hard >> r) & 1) {
+            int lmin = INT32_MAX;
+            for (int d = tid; d < D; d += SP_THREADS)
+                lmin = min(lmin, count[d]);
+            for (int off = WAVE / 2; off > 0; off >>= 1)
+                lmin = min(lmin, __shfl_down(lmin, off));
+            if (lane == 0) s_part[r][wid] = lmin;
+        } else {
+            int* cnt = s_cnt + s_sbase[r];
+            for (int d = tid; d < D; d += SP_THREADS) cnt[d] = count[d];
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int r = 0; r < n_rules; ++r) {
+            int m = INT32_MAX;
+            if ((hard >> r) & 1)
+                for (int w = 0; w < SP_WAVES; ++w) m = min(m, s_part[r][w]);
+            s_m[r] = m;
+        }
+    }
+    __syncthreads();
+    sm_recount(rules, hard, s_open, s_base, s_m, s_part);
+    __syncthreads();
+    if (tid == 0) sm_fold(hard, s_atmin, s_part);
+
+    const int budget = s_budget;
+    for (int it = 0; it < budget; ++it) {
+        unsigned long long loc = 0ull;
+        // the score and the domain ids are loaded unconditionally, four
+        // nodes in flight, so that the loads overlap
+#pragma unroll 4
+        for (int i = tid; i < N; i += SP_THREADS) {
+            const float s = score[i];
+            int dom[SM_RULES];
+#pragma unroll
+            for (int r = 0; r < SM_RULES; ++r)
+                dom[r] = r < n_rules ? rules.r[r].dom_of[i] : 0;
+            // only a live node has its domains inside [0, D_r)
+            const bool live = s > NEG_INF;
+            bool open = live;
+            float pen = 0.0f;
+#pragma unroll
+            for (int r = 0; r < SM_RULES; ++r) {
+                if (r >= n_rules) continue;
+                const int d = live ? dom[r] : 0;
+                if ((hard >> r) & 1)
+                    open &= sm_open(s_open + s_base[r], d);
+                else
+                    pen = fmaf(s_tw[r], (float)s_cnt[s_sbase[r] + d], pen);
+            }
+            if (open) {
+                const float total = s - pen;
+                const unsigned long long k = spread_key(total, i);
+                if (k > loc) loc = k;
+            }
+        }
+        loc = wave_max_u64(loc);
+        if (lane == 0) s_wkey[wid] = loc;
+        __syncthreads();
+        if (wid == 0) {
+            unsigned long long k = lane < SP_WAVES ? s_wkey[lane] : 0ull;
+            for (int off = SP_WAVES / 2; off > 0; off >>= 1) {
+                unsigned long long o = __shfl_down(k, off);
+                k = o > k ? o : k;
+            }
+            // lane 0 of wave 0 is thread 0, the only writer of the counters,
+            // the log, slot, the counts in global memory and in s_cnt, the
+            // closing bits, s_m / s_atmin and the winner's score
+            if (lane == 0) {
+                int go = 0, recount = 0;
+                if (k != 0ull) {
+                    const int node = spread_key_node(k);
+                    int sl = slot[node];
+                    if (sl >= 0 || s_cursor < s_args.K) {
+                        go = 1;
+                        // one thread, a uniform r: the rule is read from
+                        // the kernel arguments by index, not unrolled
+                        for (int r = 0; r < n_rules; ++r) {
+                            const int d = rules.r[r].dom_of[node];
+                            if (!((hard >> r) & 1)) {
+                                s_cnt[s_sbase[r] + d] += 1;
+                                continue;
+                            }
+                            const int c = rules.r[r].count[d];
+                            const int m = s_m[r];
+                            rules.r[r].count[d] = c + 1;
+                            // one more would break the skew: shut
+                            if (c + 2 - m > rules.r[r].skew)
+                                s_open[s_base[r] + (d >> 5)] &=
+                                    ~(1u << (d & 31));
+                            // the last domain at the minimum moved up
+                            if (c == m && --s_atmin[r] == 0) {
+                                s_m[r] = m + 1;
+                                recount |= 1 << r;
+                            }
+                        }
+                        int kst = 1;
+                        if (sl < 0) {
+                            sl = s_cursor;
+                            s_cursor = sl + 1;
+                            slot[node] = sl;
+                            log_nodes[sl] = node;
+                        } else {
+                            kst = log_counts[sl] + 1;
+                        }
+                        log_counts[sl] = kst;
+                        if (kst >= cap[node]) {
+                            score[node] = NEG_INF;
+                        } else if (s_args.rescore) {
+                            const SrScoreArgs a = s_args.sc;
+                            score[node] = node_score_one<false>(
+                                node, a.alloc, a.used, a.extra, nullptr,
+                                nullptr, nullptr, a.req, 0, nullptr, nullptr,
+                                a.w_least, a.w_most, a.w_bal, a.dim_w,
+                                a.wsum, a.bias, N, R, 0, kst).s;
+                        }
+                        s_total += 1;
+                    }
+                }
+                s_go = go;
+                s_recount = recount;
+            }
+        }
+        __syncthreads();
+        if (!s_go) break;               // block-uniform
+        const int rc = s_recount;       // block-uniform
+        if (rc != 0) {
+            sm_recount(rules, rc, s_open, s_base, s_m, s_part);
+            __syncthreads();
+            if (tid == 0) sm_fold(rc, s_atmin, s_part);
+        }
+    }
+
+    __syncthreads();
+    const int total = s_total;
+    const int cursor = s_cursor;
+    const SsArgs a = s_args;
+    const bool revert = (a.fuse_min >= 0) && (total < a.fuse_min);
+
+    if (revert) {
+        // single-class gang failed: nothing was applied to `used` yet; the
+        // hard rules get their placements back, the soft counts were never
+        // written
+        for (int e = tid; e < cursor; e += SP_THREADS) {
+            const int node = log_nodes[e];
+            const int cnt = log_counts[e];
+            for (int r = 0; r < n_rules; ++r)
+                if ((hard >> r) & 1)
+                    atomicSub(rules.r[r].count + rules.r[r].dom_of[node],
+                              cnt);
+            log_counts[e] = 0;
+        }
+        if (tid == 0) { *a.log_len = cursor; *a.placed = 0; }
+    } else {
+        for (int r = 0; r < n_rules; ++r) {
+            if ((hard >> r) & 1) continue;
+            const int* cnt = s_cnt + s_sbase[r];
+            for (int d = tid; d < rules.r[r].D; d += SP_THREADS)
+                rules.r[r].count[d] = cnt[d];
+        }
+        dev_commit_log(log_nodes, log_counts, cursor, total, a.sc.req,
+                       const_cast<float*>(a.sc.used), a.queue_alloc,
+                       a.log_len, a.placed, a.job_placed, N, R);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Inter-pod (anti-)affinity over a topology key, enforced before EVERY
 // placement — oracle: reference.py affinity_select_commit.  Unlike spread
 // this needs no per-instance loop: for both modes the per-placement rule
@@ -3084,6 +3399,37 @@ void vamd_spread_rescore_select(
                        log_counts, log_len, placed, job_placed, rules,
                        fuse_min, (int*)slot, N, R, K);
 }
+
+void vamd_spread_soft_select(
+    const float* alloc, float* used, const float* extra, const float* req,
+    float w_least, float w_most, float w_bal, const float* dim_w,
+    const float* bias, float* score, const int* cap, int ntasks,
+    float* queue_alloc, const float* queue_limit, int* log_nodes,
+    int* log_counts, int* log_len, int* placed, int* job_placed,
+    VamdSpreadRules rules, VamdSpreadWeights weights, int rescore,
+    int fuse_min, void* slot, int N, int R, int K, hipStream_t stream)
+{
+    // the hard rules within the limit of vamd_spread_multi_select, the soft
+    // ones within the count table: a set outside either is launched with no
+    // rule at all, which places nothing and reports zero
+    long long hard = 0, soft = 0;
+    for (int r = 0; r < rules.n && r < SM_RULES; ++r) {
+        const long long D = rules.r[r].D > 0 ? rules.r[r].D
+                                             : SM_LDS_DOMAINS + 1;
+        if (weights.tw[r] == 0.f) hard += D; else soft += D;
+    }
+    if (rules.n < 1 || rules.n > SM_RULES || hard > SM_LDS_DOMAINS ||
+            soft > SS_LDS_DOMAINS)
+        rules.n = 0;
+    hipLaunchKernelGGL(vamd::spread_soft_select_kernel, dim3(1),
+                       dim3(SP_THREADS), 0, stream, alloc, used, extra, req,
+                       w_least, w_most, w_bal, dim_w, bias, score, cap,
+                       ntasks, queue_alloc, queue_limit, log_nodes,
+                       log_counts, log_len, placed, job_placed, rules, weights,
+                       rescore != 0, fuse_min, (int*)slot, N, R, K);
+}
+
+int vamd_spread_soft_lds_domains(void) { return SS_LDS_DOMAINS; }
 
 int vamd_device_max_cards(void) { return vamd::CardPolicy::WIDTH; }
 

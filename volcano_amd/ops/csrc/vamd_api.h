@@ -200,6 +200,41 @@ __attribute__((weak)) void vamd_spread_rescore_select(
     VamdSpreadRules rules, int fuse_min, void* slot, int N, int R, int K,
     hipStream_t stream);
 
+// --- soft topology spread (whenUnsatisfiable: ScheduleAnyway) ----------------
+//
+// One f32 weight per rule of a VamdSpreadRules, passed by value beside it:
+// tw[r] == 0 marks rule r hard, anything else soft.
+struct VamdSpreadWeights {
+    float tw[VAMD_SPREAD_MAX_RULES];
+};
+
+// vamd_spread_rescore_select with soft rules among its 1..4.  A hard rule
+// filters on its skew as there.  A soft rule never filters on counts (a node
+// without its label is still out); before EVERY placement a node's key is
+// score - pen, pen = fma(tw_R, float(count_R[dom_R]), ... fma(tw_1,
+// float(count_1[dom_1]), 0)) over the soft rules in rule order, the best key
+// among the nodes open under every hard rule wins (ties to the lower index),
+// and every rule's count rises.  With `rescore` nonzero the chosen node is
+// scored again as in vamd_spread_rescore_select; otherwise its score stays
+// until its capacity is used up.  A fused gang that misses fuse_min gives
+// every rule its counts back.  Limits: sum of D over the hard rules <=
+// vamd_spread_multi_lds_domains(), over the soft rules <=
+// vamd_spread_soft_lds_domains(); a set outside them places nothing.
+// After vamd_score_cap and any cap launcher; ONE workgroup; `score` is
+// consumed, `cap` only read; `slot` holds 4*N bytes.  Weak: the runner calls
+// it only for a class with a nonzero row in class_spread_soft.
+__attribute__((weak)) void vamd_spread_soft_select(
+    const float* alloc, float* used, const float* extra, const float* req,
+    float w_least, float w_most, float w_bal, const float* dim_w,
+    const float* bias, float* score, const int* cap, int ntasks,
+    float* queue_alloc, const float* queue_limit, int* log_nodes,
+    int* log_counts, int* log_len, int* placed, int* job_placed,
+    VamdSpreadRules rules, VamdSpreadWeights weights, int rescore,
+    int fuse_min, void* slot, int N, int R, int K, hipStream_t stream);
+
+// Largest sum of D over the soft rules of one vamd_spread_soft_select.
+__attribute__((weak)) int vamd_spread_soft_lds_domains(void);
+
 // --- per-unit packing: GPU slices on cards, CPU requests on NUMA zones ------
 //
 // A pod takes its request from the units of a node; the rule is the host's
@@ -415,6 +450,10 @@ struct VamdCycle {
     // with a nonzero flag runs vamd_spread_rescore_select, for one rule or
     // several
     const int32_t* class_spread_rescore;  // HOST [C]
+    // live when set (and the domain-rule block is): row c holds one weight
+    // per rule of spread class c, in the order of class_spread_rules (or rule
+    // 0 alone); a row with a nonzero weight runs vamd_spread_soft_select
+    const float* class_spread_soft;  // HOST [C, VAMD_SPREAD_MAX_RULES]
 };
 
 // Device copies of the descriptor arrays (chain and megacycle paths).
@@ -498,6 +537,12 @@ void vamd_megacycle(const VamdCycle& cy, const VamdDevDescs& dd,
 //     scratch).  The caps before, the commits after and the multi-class
 //     reverts are those of the select it replaces.  With the column null
 //     nothing changes a single launch.
+//   * A spread class whose class_spread_soft row has a nonzero weight runs
+//     vamd_spread_soft_select where any of the three selects above would
+//     stand, with class_spread_rescore[c] as its re-score flag.  A class with
+//     only soft rules carries rule 0 in class_group / class_skew with a skew
+//     that never binds.  Everything around the select is unchanged.  With
+//     the column null nothing changes a single launch.
 // Returns 0; nonzero, before any HIP call, when cy->struct_size is not
 // sizeof(VamdCycle).
 int vamd_run_cycle(const VamdCycle* cy, hipStream_t stream);

@@ -13,11 +13,13 @@ from ctypes import (POINTER, Structure, c_float, c_int, c_int32, c_int64,
                     c_uint64, c_void_p)
 from typing import Optional
 
+import numpy as np
 import torch
 
 from .build import LIB_PATH, build
 from .reference import (DEV_MAX_CARDS, NUMA_MAX_ZONES, SPREAD_MAX_RULES,
-                        SPREAD_MULTI_LDS_DOMAINS, check_device_request,
+                        SPREAD_MULTI_LDS_DOMAINS, SPREAD_SOFT_LDS_DOMAINS,
+                        check_device_request,
                         check_hypernode_table, check_numa_request)
 
 _lib = None
@@ -56,6 +58,11 @@ class VamdSpreadRules(Structure):
                 ("n", c_int32), ("_pad", c_int32)]
 
 
+class VamdSpreadWeights(Structure):
+    """Mirror of ``VamdSpreadWeights`` in ``vamd_api.h``, passed by value."""
+    _fields_ = [("tw", c_float * SPREAD_MAX_RULES)]
+
+
 class VamdCycle(Structure):
     """Mirror of ``VamdCycle`` in ``vamd_api.h`` (same order, same types)."""
     _fields_ = [("struct_size", c_uint64)] + [
@@ -79,7 +86,8 @@ class VamdCycle(Structure):
         ("zone_Z", c_int32), ("_pad3", c_int32),
         ("class_spread_rules", c_void_p),
         ("class_rescore", c_void_p), ("rescore_slot", c_void_p),
-        ("class_spread_rescore", c_void_p)]
+        ("class_spread_rescore", c_void_p),
+        ("class_spread_soft", c_void_p)]
 
 
 def _load():
@@ -122,6 +130,13 @@ def _load():
             "volcano_amd.ops.build)")
     lib.vamd_rescore_select.restype = None
     lib.vamd_spread_rescore_select.restype = None
+    lib.vamd_spread_soft_select.restype = None
+    lib.vamd_spread_soft_lds_domains.restype = c_int
+    if lib.vamd_spread_soft_lds_domains() != SPREAD_SOFT_LDS_DOMAINS:
+        raise RuntimeError(
+            "the loaded kernel library and this module disagree on "
+            "SPREAD_SOFT_LDS_DOMAINS; rebuild (python -m "
+            "volcano_amd.ops.build)")
     lib.vamd_device_cap.restype = None
     lib.vamd_device_commit.restype = None
     lib.vamd_device_revert.restype = None
@@ -394,6 +409,57 @@ def spread_rescore_select(alloc_t, used_t, extra_t, req, w_least, w_most,
         _p(queue_limit_row), _p(log_nodes), _p(log_counts), _p(log_len),
         _p(placed), _p(job_placed), rs, c_int(int(fuse_min)), _p(slot),
         c_int(N), c_int(R), c_int(K), _stream())
+
+
+def _soft_weights(op, rules) -> VamdSpreadWeights:
+    """The ``tw`` of 1..4 ``(dom_of, dom_count, max_skew, tw)`` rules as the
+    launcher takes them, after the limits of the two LDS tables: the hard
+    rules' domains fill the bitmaps, the soft rules' the count table."""
+    tws = [float(tw) for _, _, _, tw in rules]
+    if not np.isfinite(tws).all():
+        raise ValueError(f"{op}: the weights must be finite")
+    soft = sum(c.shape[0] for (_, c, _, _), tw in zip(rules, tws) if tw != 0)
+    if soft > SPREAD_SOFT_LDS_DOMAINS:
+        raise ValueError(f"{op}: {soft} domains over the soft rules, at most "
+                         f"{SPREAD_SOFT_LDS_DOMAINS}")
+    return VamdSpreadWeights((c_float * SPREAD_MAX_RULES)(*tws))
+
+
+def spread_soft_select(alloc_t, used_t, extra_t, req, w_least, w_most, w_bal,
+                       dim_w, bias, score, cap, ntasks, queue_alloc_row,
+                       queue_limit_row, log_nodes, log_counts, log_len,
+                       placed, job_placed, rules, rescore, fuse_min,
+                       slot=None):
+    """``spread_rescore_select`` under 1 to 4 rules ``(dom_of, dom_count,
+    max_skew, tw)``: a rule with ``tw == 0`` is hard; one with ``tw != 0`` is
+    soft (ScheduleAnyway), never filters on counts and costs ``tw`` per
+    member already in the node's domain, before every placement.  With
+    ``rescore`` the chosen node is scored again after every placement.
+    ``score`` is consumed, ``cap`` only read; ``slot`` holds N int32."""
+    lib = _load()
+    R, N = alloc_t.shape
+    K = log_nodes.shape[0]
+    if score.shape[0] != N or cap.shape[0] != N:
+        raise ValueError("spread_soft_select: score and cap need one entry "
+                         "per node")
+    if K < 1 or log_counts.shape[0] != K:
+        raise ValueError("spread_soft_select: log_nodes/log_counts differ in "
+                         "length or are empty")
+    rules = list(rules)
+    rs = _spread_rules("spread_soft_select", [r[:3] for r in rules], N)
+    ws = _soft_weights("spread_soft_select", rules)
+    if slot is None:
+        slot = torch.empty(max(N, 1), dtype=torch.int32, device=score.device)
+    elif slot.numel() * slot.element_size() < 4 * N:
+        raise ValueError("spread_soft_select: slot smaller than 4*N bytes")
+    lib.vamd_spread_soft_select(
+        _p(alloc_t), _p(used_t), _p(extra_t), _p(req), c_float(w_least),
+        c_float(w_most), c_float(w_bal), _p(dim_w), _p(bias), _p(score),
+        _p(cap), c_int(int(ntasks)), _p(queue_alloc_row),
+        _p(queue_limit_row), _p(log_nodes), _p(log_counts), _p(log_len),
+        _p(placed), _p(job_placed), rs, ws, c_int(1 if rescore else 0),
+        c_int(int(fuse_min)), _p(slot), c_int(N), c_int(R), c_int(K),
+        _stream())
 
 
 def domain_mask(score, cap, dom_of, dom_count, mode, scratch=None):
@@ -673,7 +739,10 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
     rule 0 is also the class's ``class_group``/``class_skew``).  An optional
     ``class_rescore`` (host int32 numpy [C]) flags the spread classes whose
     chosen node is scored again after every placement
-    (``spread_rescore_select``, for one rule or several).
+    (``spread_rescore_select``, for one rule or several).  An optional
+    ``class_soft`` (host float32 numpy [C, 4]) holds one weight per rule of
+    every spread class, in the order of ``class_rules`` (or rule 0 alone): a
+    row with a nonzero weight runs ``spread_soft_select``.
 
     ``devices`` (plans with device-request classes only) is a dict: the
     card planes ``mem_used``/``cores_used``/``state`` device i32 [K, N],
@@ -764,6 +833,30 @@ def run_cycle(class_descs: bytes, n_classes: int, job_descs: bytes,
                 raise ValueError("run_cycle: spread.class_rescore must be "
                                  "int32 [C]")
             cy.class_spread_rescore = flags.ctypes.data
+        soft = spread.get("class_soft")
+        if soft is not None:
+            if soft.shape != (n_classes, SPREAD_MAX_RULES) \
+                    or soft.dtype != "float32" \
+                    or not soft.flags["C_CONTIGUOUS"]:
+                raise ValueError("run_cycle: spread.class_soft must be "
+                                 f"float32 [C, {SPREAD_MAX_RULES}]")
+            doms = spread["domains"]
+            for c in soft.any(axis=1).nonzero()[0]:
+                gs = spread["class_group"][c:c + 1]
+                if cr is not None and cr[c, 0] >= 2:
+                    gs = cr[c, 1:1 + 2 * int(cr[c, 0]):2]
+                tw = soft[c, :len(gs)]
+                if gs[0] < 0 or (mode is not None and mode[c] != 0) \
+                        or soft[c, len(gs):].any() \
+                        or not np.isfinite(tw).all() \
+                        or int(doms[gs][tw != 0].sum()) \
+                        > SPREAD_SOFT_LDS_DOMAINS:
+                    raise ValueError(
+                        f"run_cycle: class_soft row {c}: finite weights for "
+                        "the rules of a spread class only, at most "
+                        f"{SPREAD_SOFT_LDS_DOMAINS} domains over the soft "
+                        "ones")
+            cy.class_spread_soft = soft.ctypes.data
     if devices is not None:
         K, _ = _unit_planes("run_cycle", _CARDS, (
             devices["mem_used"], devices["cores_used"], devices["state"]),

@@ -788,6 +788,147 @@ def spread_rescore_select_commit(
     job_placed.add_(total)
 
 
+# largest sum of D over the SOFT rules of one spread_soft_select_commit on the
+# device (``SS_LDS_DOMAINS`` of scheduler_kernels.hip: 28 KB of int32 counts
+# in LDS; checked on load)
+SPREAD_SOFT_LDS_DOMAINS = 7168
+# maxSkew carried by a soft rule where a hard one is expected: never binds,
+# and count + 1 - min cannot overflow int32
+SPREAD_SOFT_SKEW = 1 << 30
+
+
+def spread_soft_select_commit(
+    alloc: torch.Tensor, used: torch.Tensor, extra: torch.Tensor,
+    ready: torch.Tensor, taints: torch.Tensor, planes: torch.Tensor,
+    req: torch.Tensor, tolerated: int, require: torch.Tensor,
+    forbid: torch.Tensor, w_least: float, w_most: float, w_bal: float,
+    dim_w: torch.Tensor, bias: Optional[torch.Tensor],
+    score: torch.Tensor, cap: torch.Tensor, ntasks: int,
+    queue_alloc: torch.Tensor, queue_limit: torch.Tensor,
+    log_nodes: torch.Tensor, log_counts: torch.Tensor, log_len: torch.Tensor,
+    placed: torch.Tensor, job_placed: torch.Tensor,
+    rules,                      # 1..4 x (dom_of [N] i32, dom_count [D_r] i32
+                                #         in place, max_skew >= 1, tw f32)
+    rescore: bool, fuse_min: int = -1, score_fn=None,
+) -> None:
+    """``spread_rescore_select_commit`` with ``whenUnsatisfiable:
+    ScheduleAnyway`` rules among its 1 to 4: a rule with ``tw == 0`` is hard
+    and filters on its ``maxSkew`` as there; a rule with ``tw != 0`` is soft,
+    never filters on counts (a node without its label is still out) and
+    instead costs ``tw`` per member already in the node's domain.
+
+    A plain sequential loop — the source of truth of the HIP
+    ``spread_soft_select_kernel``.  Before every single placement each
+    remaining node has ``pen = fma(tw_R, float(cnt_R[d_R]), ... fma(tw_1,
+    float(cnt_1[d_1]), 0.0))`` over the soft rules in rule order, one f32 fma
+    each, and ``total = score - pen``, one f32 subtraction.  Among the nodes
+    with ``score > -inf``, capacity left and every hard rule's domain open,
+    the highest ``total`` wins, ties to the lower index (``-0.0`` ties with
+    ``0.0``).  It takes ONE instance and its domain's count rises under every
+    rule.  With ``rescore`` its score is then recomputed as
+    ``spread_rescore_select_commit`` does; without, it stays until the
+    node's capacity is used up.  Log, budget, ``used``, counters and the
+    ``fuse_min`` discard (every rule's counts come back) are
+    ``spread_rescore_select_commit``'s."""
+    import numpy as np
+    rules = list(rules)
+    if not 1 <= len(rules) <= SPREAD_MAX_RULES:
+        raise ValueError(f"1 to {SPREAD_MAX_RULES} spread rules per class")
+    if any(int(skew) < 1 for _, _, skew, _ in rules):
+        raise ValueError("max_skew must be >= 1")
+    N = score.shape[0]
+    K = log_nodes.shape[0]
+    log_nodes.zero_()
+    log_counts.zero_()
+
+    headroom = queue_limit - queue_alloc
+    pos = req > EPS
+    per_dim = torch.where(pos, (headroom + EPS) / torch.clamp(req, min=EPS),
+                          torch.full_like(headroom, float(BIG_CAP)))
+    quota = int(per_dim.amin().clamp(min=0, max=float(BIG_CAP)).floor())
+    budget = min(int(ntasks), quota)
+
+    one_s = torch.empty(1, dtype=torch.float32, device=score.device)
+    one_c = torch.empty(1, dtype=torch.int32, device=score.device)
+
+    def formula(n: int, k: int) -> float:
+        row = slice(n, n + 1)
+        score_cap(alloc[row], fma_f32(k, req, used[row]), extra[row],
+                  torch.ones_like(ready[row]), torch.zeros_like(taints[row]),
+                  planes[row], req, 0, torch.zeros_like(require),
+                  torch.zeros_like(forbid), w_least, w_most, w_bal, dim_w,
+                  None if bias is None else bias[row], one_s, one_c)
+        return float(one_s)
+
+    again = formula if score_fn is None else score_fn
+    sc = score.detach().cpu().numpy().astype(np.float32)
+    doms = [d.detach().cpu().numpy().astype(np.int64) for d, _, _, _ in rules]
+    cnts = [c.detach().cpu().numpy().astype(np.int64) for _, c, _, _ in rules]
+    before = [c.copy() for c in cnts]
+    skews = [int(s) for _, _, s, _ in rules]
+    tws = [float(np.float32(t)) for _, _, _, t in rules]
+    rem = cap.detach().cpu().numpy().astype(np.int64)
+    rem[~(sc > NEG_INF)] = 0
+    for d in doms:
+        rem[d < 0] = 0
+    slot = {}                   # node → log entry
+    nodes: list = []
+    counts: list = []
+    total = 0
+    while total < budget:
+        ok = rem > 0
+        pen = torch.zeros(N, dtype=torch.float32)
+        for c, d, k, tw in zip(cnts, doms, skews, tws):
+            here = c[np.where(ok, d, 0)]
+            if tw == 0:
+                ok &= here + 1 - c.min() <= k
+            else:
+                pen = fma_f32(tw, torch.from_numpy(
+                    here.astype(np.float32)), pen)
+        live = np.flatnonzero(ok)
+        if live.size == 0:
+            break
+        tot = (sc - pen.numpy())[live]          # f32 - f32, one rounding
+        best = int(live[np.argmax(tot)])        # first maximum: lower index
+        e = slot.get(best)
+        if e is None:
+            if len(nodes) >= K:
+                break
+            e = slot[best] = len(nodes)
+            nodes.append(best)
+            counts.append(0)
+        counts[e] += 1
+        rem[best] -= 1
+        total += 1
+        for c, d in zip(cnts, doms):
+            c[d[best]] += 1
+        if rem[best] <= 0:
+            sc[best] = NEG_INF
+        elif rescore:
+            sc[best] = again(best, counts[e])
+            if not sc[best] > NEG_INF:
+                rem[best] = 0
+
+    m = len(nodes)
+    dev = score.device
+    idx = torch.tensor(nodes, dtype=torch.long, device=dev)
+    c32 = torch.tensor(counts, dtype=torch.int32, device=dev)
+    log_nodes[:m] = idx.to(torch.int32)
+    log_len.fill_(m)
+    discard = fuse_min >= 0 and total < fuse_min
+    for (_, dom_count, _, _), c in zip(rules, before if discard else cnts):
+        dom_count.copy_(torch.from_numpy(c.astype(np.int32)).to(dev))
+    if discard:
+        placed.fill_(0)
+        return
+    log_counts[:m] = c32
+    used.index_add_(0, idx, c32.to(torch.float32).unsqueeze(1)
+                    * req.unsqueeze(0))
+    queue_alloc += torch.tensor(float(total), device=dev) * req
+    placed.fill_(total)
+    job_placed.add_(total)
+
+
 def domain_mask(score: torch.Tensor, cap: torch.Tensor,
                 dom_of: torch.Tensor, dom_count: torch.Tensor,
                 mode: int) -> None:

@@ -689,10 +689,12 @@ class _ExactRules:
                 cp.spread = cp.spread_rules[0]
                 for g, _ in rule:
                     _clear_bit(cp, "forbid", pub.sat_bit[g])
+                cp.spread_soft = pub.soft_weights(cp.tclass.tasks[0])
             elif kind == "spread":
                 g, skew = rule
                 cp.spread = (group(g), skew)
                 _clear_bit(cp, "forbid", pub.sat_bit[g])    # saturated zones
+                cp.spread_soft = pub.soft_weights(cp.tclass.tasks[0])
             else:
                 g, mode = rule
                 cp.affinity = (group(g), mode)  # hosting set / occupied domains

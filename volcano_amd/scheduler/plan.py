@@ -124,6 +124,13 @@ class ClassPlan:
     # spread select, which holds every maxSkew before every placement.
     # Never combined with ``bundle``, ``affinity`` or ``hypernode``.
     spread_rules: Optional[List[Tuple[int, int]]] = None
+    # one f32 weight per rule of a spread class (``spread_rules``, or
+    # ``spread`` alone), 0 = hard.  A rule with a nonzero weight is soft
+    # (whenUnsatisfiable: ScheduleAnyway): it never filters on counts, costs
+    # its weight per member already in the node's domain before every
+    # placement, and carries ref.SPREAD_SOFT_SKEW as a maxSkew that never
+    # binds.  Any nonzero weight sends the class to spread_soft_select.
+    spread_soft: Optional[List[float]] = None
     # (index into CyclePlan.spread_groups, mode): inter-pod affinity
     # (mode 1) or keyed anti-affinity (mode 2) enforced per placement over
     # the group's domains — domain mask + select_commit + count update.
@@ -438,6 +445,23 @@ class CyclePlan:
             raise ValueError(f"class {c}: several spread rules never "
                              "combine with bundle, affinity or hypernode")
 
+    def check_spread_soft(self, c: int, cp: ClassPlan) -> None:
+        """``cp.spread_soft`` of class ``c`` against its rules (part of
+        ``finalize``)."""
+        if cp.spread_soft is None:
+            return
+        rules = cp.spread_rules or ([cp.spread] if cp.spread else [])
+        tws = np.asarray(cp.spread_soft, dtype=np.float32)
+        if tws.shape != (len(rules),) or not rules \
+                or not np.isfinite(tws).all():
+            raise ValueError(f"class {c}: one finite weight per spread rule")
+        if sum(self.spread_groups[g].count.shape[0]
+               for (g, _), tw in zip(rules, tws) if tw != 0) \
+                > ref.SPREAD_SOFT_LDS_DOMAINS:
+            raise ValueError(
+                f"class {c}: its soft spread rules have more than "
+                f"{ref.SPREAD_SOFT_LDS_DOMAINS} domains in all")
+
     def finalize(self) -> None:
         """Assign undo-log slots (one contiguous region per class),
         normalize constraint widths (the label-bit registry may have
@@ -485,6 +509,7 @@ class CyclePlan:
                     raise ValueError(f"class {c}: spread classes never "
                                      "bundle")
             self.check_spread_rules(c, cp)
+            self.check_spread_soft(c, cp)
             if cp.affinity is not None:
                 g, mode = cp.affinity
                 if not 0 <= g < len(self.spread_groups):
@@ -533,6 +558,14 @@ class CyclePlan:
         self.class_spread_rescore = np.array(
             [1 if cp.rescore and cp.spread is not None else 0
              for cp in self.classes], dtype=np.int32)
+        # one weight per rule of the spread classes; a row with a nonzero
+        # weight takes spread_soft_select
+        self.class_spread_soft = np.zeros(
+            (len(self.classes), ref.SPREAD_MAX_RULES), dtype=np.float32)
+        for c, cp in enumerate(self.classes):
+            if cp.spread_soft is not None:
+                self.class_spread_soft[c, :len(cp.spread_soft)] = \
+                    cp.spread_soft
         lens = np.fromiter((jp.class_end - jp.class_begin
                             for jp in self.jobs), dtype=np.int64,
                            count=len(self.jobs))
@@ -666,7 +699,20 @@ def run_plan_torch(plan: CyclePlan) -> CycleResult:
                 # u + c*r - c*r is not u in f32 once usage comes in bytes
                 used_before = used.clone()
                 qa_before = plan.queue_alloc[cp.queue_idx].clone()
-            if plan.class_spread_rescore[c]:
+            if plan.class_spread_soft[c].any():
+                rules = cp.spread_rules or [cp.spread]
+                ref.spread_soft_select_commit(
+                    alloc, used, extra, nt.ready.bool(), nt.taint_mask,
+                    planes, req, cp.tolerated, require, forbid, cp.w_least,
+                    cp.w_most, cp.w_bal, dim_w, b, score, cap, cp.ntasks,
+                    plan.queue_alloc[cp.queue_idx],
+                    plan.queue_limit[cp.queue_idx],
+                    log_nodes[sl], log_counts[sl], log_len[c],
+                    class_placed[c], job_placed[j],
+                    [(sp_dom[g], sp_cnt[g], k, tw) for (g, k), tw in
+                     zip(rules, plan.class_spread_soft[c])],
+                    bool(plan.class_spread_rescore[c]))
+            elif plan.class_spread_rescore[c]:
                 ref.spread_rescore_select_commit(
                     alloc, used, extra, nt.ready.bool(), nt.taint_mask,
                     planes, req, cp.tolerated, require, forbid, cp.w_least,
@@ -909,6 +955,9 @@ def run_plan_hip(plan: CyclePlan) -> CycleResult:
         # host-side for the runner and exists only when the plan has one
         if plan.class_spread_rescore.any():
             spread["class_rescore"] = plan.class_spread_rescore
+        # so do the weights of the classes with a soft rule
+        if plan.class_spread_soft.any():
+            spread["class_soft"] = plan.class_spread_soft
         plan.spread_counts = [count[int(o):int(o) + int(d)]
                               for o, d in zip(offs, lens)]
 

@@ -3,8 +3,9 @@
 Weighted sum of leastrequested / mostrequested / balancedallocation — the
 three analytic terms of the fused score kernel (K2).  Taint-toleration and
 affinity hard filters are handled by the predicates plugin's bit planes;
-the soft (preferred) variants contribute to the same score via the bias
-plane when configured.
+a soft topology-spread entry (``whenUnsatisfiable: ScheduleAnyway``) is
+scored per placement by the topologyspread plugin's own select
+(``exact: true`` there), not here.
 
 The select scores a class once and fills nodes in that order; the reference
 scores per task, so a node that just took a pod scores lower (or higher) for

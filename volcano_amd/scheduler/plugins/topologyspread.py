@@ -45,6 +45,21 @@ keeps the cycle-granular bits for that class (logged once).
 ``exact`` is ignored — the cycle-granular path above is used — for jobs
 with a SubGroupPolicy and for runs under the soft-shard coordinator:
 both can drop placements after the kernel has counted them.
+
+An entry with ``whenUnsatisfiable: "ScheduleAnyway"`` is SOFT (anything
+else, absence included, is ``DoNotSchedule``).  It never filters on counts:
+it sets no saturation bit and does not enter the session-open floor; only
+its unlabeled nodes stay out of bounds.  With ``exact: true`` it is scored
+per placement on the device (``spread_soft_select_commit`` /
+``spread_soft_select_kernel``): every member already in a node's domain
+costs the node ``soft.weight / 100`` of score (plugin argument
+``soft.weight``, default 2.0 — the reference's podtopologyspread weight on
+its 0-100 scale against the 0-1 score terms here).  ``resolve_task`` names a
+soft rule with ``SPREAD_SOFT_SKEW`` as a maxSkew that never binds, and
+``soft_weights`` gives the per-rule weights beside it (0 = hard).  Without
+``exact``, where ``exact`` is ignored, or when the soft rules of a class have
+more than ``SPREAD_SOFT_LDS_DOMAINS`` domains in all, a soft entry adds no
+score (logged once).
 """
 
 from __future__ import annotations
@@ -56,7 +71,8 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from ...api.types import TaskStatus
-from ...ops.reference import SPREAD_MAX_RULES, SPREAD_MULTI_LDS_DOMAINS
+from ...ops.reference import (SPREAD_MAX_RULES, SPREAD_MULTI_LDS_DOMAINS,
+                              SPREAD_SOFT_LDS_DOMAINS, SPREAD_SOFT_SKEW)
 from ..tensors import set_plane_bit
 from .base import Plugin, register
 
@@ -85,12 +101,20 @@ def _specs(pod) -> list:
     return out
 
 
-def _log_once(specs, why: str) -> None:
+def _soft(e) -> bool:
+    """``whenUnsatisfiable: ScheduleAnyway`` — everything else is hard."""
+    return e.get("whenUnsatisfiable") == "ScheduleAnyway"
+
+
+def _log_once(specs, why: str,
+              then: str = "the class keeps the cycle-granular path") -> None:
     key = tuple((e["group"], e["topologyKey"]) for e in specs)
-    if key not in _LOGGED:
-        _LOGGED.add(key)
-        log.warning("topologyspread: %s for %s; the class keeps the "
-                    "cycle-granular path", why, list(key))
+    if (key, then) not in _LOGGED:
+        _LOGGED.add((key, then))
+        log.warning("topologyspread: %s for %s; %s", why, list(key), then)
+
+
+_UNSCORED = "its ScheduleAnyway entries add no score"
 
 
 def _truthy(v) -> bool:
@@ -102,7 +126,9 @@ def _truthy(v) -> bool:
 class SpreadExact:
     """What ``exact: true`` publishes on the session (``ssn.spread_exact``)."""
 
-    def __init__(self):
+    def __init__(self, soft_tw: float = 0.02):
+        self.soft_tw = soft_tw               # score per member, soft rules
+        self._soft_memo: Dict[object, Optional[list]] = {}
         self.keys: List[tuple] = []          # (group, topologyKey) per index
         self.dom_of: List[np.ndarray] = []   # [N] i32 per group
         self.count: List[np.ndarray] = []    # [D] i32 per group
@@ -120,7 +146,8 @@ class SpreadExact:
     def resolve_task(self, task):
         """(group index, maxSkew >= 1) of a task's class; with several
         constraints the list of all of them; None when there is none or
-        the class stays cycle-granular."""
+        the class stays cycle-granular.  A soft entry is a rule with
+        ``SPREAD_SOFT_SKEW``; ``soft_weights`` tells which."""
         sig = task.class_signature()
         got = self._memo.get(sig, self)
         if got is not self:
@@ -128,9 +155,20 @@ class SpreadExact:
         out = None
         specs = _specs(task.pod)
         gs = [self._index.get((s["group"], s["topologyKey"])) for s in specs]
+        soft = [g for g, s in zip(gs, specs) if _soft(s) and g is not None]
+        if sum(len(self.count[g]) for g in soft) > SPREAD_SOFT_LDS_DOMAINS:
+            # the soft entries leave; the hard ones stay exact
+            _log_once(specs, f"more than {SPREAD_SOFT_LDS_DOMAINS} domains "
+                             "over the soft constraints", _UNSCORED)
+            keep = [i for i, s in enumerate(specs) if not _soft(s)]
+            specs, gs = [specs[i] for i in keep], [gs[i] for i in keep]
+        tws = None
         if specs and None not in gs:
-            rules = [(g, max(1, int(s.get("maxSkew", 1))))
+            rules = [(g, SPREAD_SOFT_SKEW if _soft(s)
+                      else max(1, int(s.get("maxSkew", 1))))
                      for g, s in zip(gs, specs)]
+            if any(_soft(s) for s in specs):
+                tws = [self.soft_tw if _soft(s) else 0.0 for s in specs]
             if len(rules) == 1:
                 out = rules[0]
             elif len(rules) > SPREAD_MAX_RULES:
@@ -142,7 +180,14 @@ class SpreadExact:
             else:
                 out = rules
         self._memo[sig] = out
+        self._soft_memo[sig] = tws if out is not None else None
         return out
+
+    def soft_weights(self, task) -> Optional[list]:
+        """One f32 weight per rule of ``resolve_task(task)``, 0 for a hard
+        rule; None when the class has no soft rule."""
+        self.resolve_task(task)
+        return self._soft_memo.get(task.class_signature())
 
     def resolve(self, tclass, job=None):
         return self.resolve_task(tclass.tasks[0])
@@ -153,6 +198,8 @@ class TopologySpreadPlugin(Plugin):
     def on_session_open(self, ssn) -> None:
         nt = ssn.node_tensors
         exact = _truthy(self.args.get("exact", False))
+        soft_tw = float(np.float32(
+            float(self.args.get("soft.weight", 2.0)) / 100.0))
 
         # group → topology value → placed member count
         counts: Dict[tuple, Dict[str, int]] = defaultdict(
@@ -182,7 +229,7 @@ class TopologySpreadPlugin(Plugin):
 
         bits: Dict[tuple, int] = {}
         unl_bits: Dict[tuple, int] = {}
-        published = SpreadExact() if exact else None
+        published = SpreadExact(soft_tw) if exact else None
         for gk, s in specs.items():
             group, key = gk
             max_skew = int(s.get("maxSkew", 1))
@@ -191,12 +238,15 @@ class TopologySpreadPlugin(Plugin):
                 continue
             cnt = counts.get(gk, {})
             floor = min((cnt.get(v, 0) for v in vals), default=0)
-            saturated = [v for v in vals
-                         if cnt.get(v, 0) >= floor + max_skew]
+            # a soft constraint never filters on counts
+            saturated = [] if _soft(s) else [
+                v for v in vals if cnt.get(v, 0) >= floor + max_skew]
             # nodes without the topology label are always out of bounds
             unlabeled = [ni.node_id for ni in ssn.nodes.values()
                          if ni.node.meta.labels.get(key) is None]
             if not exact:
+                if _soft(s):
+                    _log_once([s], "exact is off", _UNSCORED)
                 ids = unlabeled + [nid for v in saturated
                                    for nid in vals[v]]
                 if ids:
@@ -223,7 +273,9 @@ class TopologySpreadPlugin(Plugin):
         def hook(tclass, job, require, forbid):
             for s in _specs(tclass.tasks[0].pod):
                 gk = (s["group"], s["topologyKey"])
-                for bit in (bits.get(gk), unl_bits.get(gk)):
+                # exact: a soft entry takes the unlabeled bit alone
+                sat = None if exact and _soft(s) else bits.get(gk)
+                for bit in (sat, unl_bits.get(gk)):
                     if bit is not None:
                         set_plane_bit(forbid, bit)
 
